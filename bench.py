@@ -1,7 +1,14 @@
 """Benchmark: 6DOF env-steps/s of the fused HIP step at N envs per GPU (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n ENVS_PER_GPU] [--model 6DOF|3DOF]
-                    [--allgather] [--gather-leg | --no-gather-leg] [--no-sb3-legs] [--cpu-seconds S]
+                    [--dump-outputs DIR] [--full] [--allgather] [--gather-leg | --no-gather-leg]
+                    [--no-sb3-legs] [--cpu-seconds S]
+
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, the K timed
+steps, the outputs of the last timed step written to DIR (``--dump-outputs``), the result line.
+``--full`` adds every other leg to the line: the N sweep, the CPU baselines, the wall-clock legs
+through the Python boundary, at more than one rank the step + all_gather leg, and in rollout
+mode the PPO update and training-iteration legs.
 
 A "step" = one launch of the fused step kernel over all N envs of a GPU: action in,
 RK4 rigid-body step + ground event + reward + done + obs + TimeLimit + auto-reset out.
@@ -44,6 +51,8 @@ AUTO_LOOP_MAX_K = 8
 # warm-up of the n_sweep points: past the first episode ends, so that their K steps include the
 # done path (terminal rows, auto-reset) at its steady rate
 SWEEP_MIN_WARMUP = 100
+FULL_N_SWEEP = "4096,524288,4194304"  # --n-sweep of a --full run
+DUMP_BUDGET = 64 * 10 ** 6  # --dump-outputs: bytes written at most, file headers included
 REFERENCE_PY_STEP = {"6DOF": 569, "3DOF": 3396}  # SURVEY.md §6, survey container, 1 core
 
 
@@ -53,6 +62,14 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--n", type=int, default=65536, help="envs per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline: the N sweep, the CPU baselines, the SB3-facing wall-clock "
+                         "legs, the step + all_gather leg at more than one rank, the rollout mode's PPO legs "
+                         "(default: the headline's timed region only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32; at most %d MB in all: of a larger output a fixed, seeded sample "
+                         "of the envs, their indices in DIR/env_index.npy)" % (DUMP_BUDGET // 10 ** 6))
     ap.add_argument("--model", default="6DOF")
     ap.add_argument("--integrator", default="rk4")
     ap.add_argument("--allgather", action="store_true",
@@ -81,8 +98,9 @@ def parse(argv=None):
                     help="skip the wall-clock legs through the Python boundary (RocketVecEnv.step with host and "
                          "device outputs, the single-env gym Rocket6DOF.step)")
     ap.add_argument("--sb3-steps", type=int, default=100)
-    ap.add_argument("--n-sweep", default="4096,524288,4194304",
-                    help="other envs-per-GPU points of the north star's N in {4k, 64k, 512k}, plus 4M (a ~1 GB "
+    ap.add_argument("--n-sweep", default=None,
+                    help="(default with --full: %s; otherwise none) other envs-per-GPU points" % FULL_N_SWEEP +
+                         " of the north star's N in {4k, 64k, 512k}, plus 4M (a ~1 GB "
                          "working set, 4x the 256 MB MALL: the true-HBM reading SURVEY.md 8d asks for), timed with "
                          "the same protocol (K steps after W warm-up, max over ranks) and reported in the line's "
                          "n_sweep (empty: none)")
@@ -394,6 +412,10 @@ def bench_rollout(args, dev, n, model, kw, dist=None, rank=0, world=1):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     steps = reps * args.rollout_steps
+    if args.dump_outputs and rank == 0:
+        # what collect() leaves its caller: the rollout buffer of the last timed collect
+        dump_outputs(args.dump_outputs, {k: (getattr(ro, k), 1) for k in (
+            "obs", "actions", "rewards", "starts", "values", "log_probs", "advantages", "returns")}, n)
     # The PPO update (SB3 1.6 PPO.train on the device-resident rollout, batch_size = N: n_steps
     # minibatches per epoch; one policy replica per GPU, minibatch gradients averaged over the
     # ranks with one all_reduce): eager PyTorch (one warm-up epoch, then one timed epoch) and the
@@ -411,11 +433,12 @@ def bench_rollout(args, dev, n, model, kw, dist=None, rank=0, world=1):
         return time.perf_counter() - t1, out
 
     update, stats, train = None, None, None
-    if not args.no_ppo:
+    ppo = args.full and not args.no_ppo  # the update legs belong to a --full run
+    if ppo:
         ppo_update(pol, opt, ro, n_epochs=1, batch_size=n, group=grp)
         upd, stats = timed(lambda: ppo_update(pol, opt, ro, n_epochs=1, batch_size=n, group=grp))
         update = {"minibatches_per_epoch": args.rollout_steps, "batch_size": n, "eager_epoch_ms": upd * 1e3}
-    if not args.no_ppo and (dist is None or dist.get_backend() == "nccl"):
+    if ppo and (dist is None or dist.get_backend() == "nccl"):
         gt = GraphedPPOUpdate(pol, opt, ro, batch_size=n, group=grp, fused=False)
         gt.update(n_epochs=1)
         gupd, _ = timed(lambda: gt.update(n_epochs=3))
@@ -967,8 +990,31 @@ def gather_leg_result(args, env, pool, dev, dist, backend, launch, n, world, K):
                 "(obs, reward, done) per step, the global batch on every rank (ShardGather.step)"}
 
 
+def dump_outputs(path, arrays, n_envs):
+    """--dump-outputs: {name: (device tensor, its env axis)} as `path`/<name>.npy in float32 (the
+    uint8 flags as 0 / 1). Where they exceed DUMP_BUDGET bytes together, every array keeps the same
+    sorted sample of the envs, drawn by a fixed seed, and env_index.npy (float64) lists it."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    total = sum(4 * t.numel() for t, _ in arrays.values())
+    room = DUMP_BUDGET - 128 * (len(arrays) + 1)  # less one .npy header per file
+    idx = None
+    if total > room:
+        keep = max(1, int(room / (total / n_envs + 8)))  # an env's rows in every array + its index
+        idx = np.sort(np.random.default_rng(0).choice(n_envs, keep, replace=False))
+        np.save(os.path.join(path, "env_index.npy"), idx.astype(np.float64))
+    for name, (t, axis) in arrays.items():
+        a = t.detach().cpu().numpy().astype(np.float32)
+        if idx is not None:
+            a = np.take(a, idx, axis=axis)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
+    if args.n_sweep is None:
+        args.n_sweep = FULL_N_SWEEP if args.full else ""
     plan, msg = launch_plan(args.gpus, os.environ)
     if plan == "error":
         print(msg, file=sys.stderr, flush=True)
@@ -990,7 +1036,8 @@ def main():
     backend = os.environ.get("RR_BENCH_BACKEND", "nccl")
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    gather_leg = args.mode == "step" and not args.allgather and not args.no_gather_leg and (world > 1 or args.gather_leg)
+    gather_leg = args.mode == "step" and not args.allgather and not args.no_gather_leg and \
+        ((world > 1 and args.full) or args.gather_leg)
     dist = None
     if world == 1 and (args.allgather or gather_leg):  # step + gather on one GPU (a rehearsal of the collective)
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -1156,6 +1203,14 @@ def main():
         result["roofline_fp64"] = stored_exact_fp64(n)
 
     # ---- the step + all_gather leg (reported separately from the step alone) ----
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs as its caller holds them: the env's own output tensors
+        # (RocketBatch.step) or, with --allgather, the gathered global batch (ShardGather.step)
+        src = gather if gather is not None else env
+        outs = {"obs": (src.obs, 0), "reward": (src.reward, 0), "done": (src.done, 0)}
+        if gather is None:
+            outs["truncated"] = (env.truncated, 0)
+        dump_outputs(args.dump_outputs, outs, src.obs.shape[0])
     if launch == "isolated":
         result["roofline"]["isolated_median_us"] = reg["isolated_median_ms"] * 1e3
         result["roofline"]["isolated_min_us"] = reg["isolated_min_ms"] * 1e3
@@ -1194,9 +1249,9 @@ def main():
                 result["n_sweep"][-1]["per_rank"] = r_i["per_rank"]
                 result["n_sweep"][-1]["per_rank_wall_max_over_min"] = max(walls) / min(walls)
             e_i.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baselines(model, args.cpu_seconds, host_cores())
-    if rank == 0 and world == 1 and model == 6 and not args.no_sb3_legs and args.integrator == "rk4":
+    if args.full and rank == 0 and world == 1 and model == 6 and not args.no_sb3_legs and args.integrator == "rk4":
         result["sb3_legs"] = sb3_legs(dev, n, args.sb3_steps)
     if rank == 0:
         print(json.dumps(result), flush=True)

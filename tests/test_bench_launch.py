@@ -189,3 +189,48 @@ def test_committed_traces_of_another_launch_mode_are_not_quoted(tmp_path, monkey
     assert traffic == 4500.0 * 1000  # lower median of five
     assert bench.launch_kind("graph") == "graph" and bench.launch_kind("direct: tools/x") == "direct"
     assert bench.launch_kind("rr_step per step") == "eager"
+
+
+def test_plain_run_is_the_headline_only():
+    """Without --full no leg beside the headline is asked for; --full restores the N sweep, and an
+    explicit --n-sweep holds either way."""
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not a.full and a.n_sweep is None and a.dump_outputs is None
+    assert bench.parse(["--full"]).full
+    assert bench.parse(["--n-sweep", "4096"]).n_sweep == "4096"
+    assert [int(x) for x in bench.FULL_N_SWEEP.split(",")] == [4096, 524288, 4194304]
+
+
+def test_dump_outputs_keeps_one_seeded_env_sample_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 arrays as given while they fit the budget; past it every array keeps
+    the same sorted env sample (on its own env axis), the same one from run to run."""
+    import torch
+
+    import bench
+
+    n = 1000
+    obs = torch.arange(n * 14, dtype=torch.float32).reshape(n, 14)
+    done = (torch.arange(n) % 3 == 0).to(torch.uint8)
+    buf = torch.arange(4 * n * 3, dtype=torch.float32).reshape(4, n, 3)
+    arrays = {"obs": (obs, 0), "done": (done, 0), "buf": (buf, 1)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays, n)
+    assert sorted(os.listdir(tmp_path / "all")) == ["buf.npy", "done.npy", "obs.npy"]
+    d = np.load(tmp_path / "all" / "done.npy")
+    assert d.dtype == np.float32 and np.array_equal(d, done.numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "buf.npy"), buf.numpy())
+    budget = 40000
+    monkeypatch.setattr(bench, "DUMP_BUDGET", budget)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, n)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["buf.npy", "done.npy", "env_index.npy", "obs.npy"]
+    assert budget // 2 < sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    idx = np.load(tmp_path / "a" / "env_index.npy")
+    assert idx.dtype == np.float64 and len(idx) > 100 and np.all(np.diff(idx) > 0)
+    idx = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "obs.npy"), obs.numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "buf.npy"), buf.numpy()[:, idx])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

@@ -32,7 +32,7 @@ run() {  # run NAME REP [N]
     RR_LIB_PATH="$R/tools/ab/lib_$1.so" timeout -k 10 200 python bench.py --mode rollout --steps 320 --no-ppo \
       > "$OUT/$tag.json" 2> "$OUT/$tag.err"
   elif [ "$MODE" = ppo ]; then
-    RR_LIB_PATH="$R/tools/ab/lib_$1.so" timeout -k 10 300 python bench.py --mode rollout --steps 32 \
+    RR_LIB_PATH="$R/tools/ab/lib_$1.so" timeout -k 10 300 python bench.py --full --mode rollout --steps 32 \
       > "$OUT/$tag.json" 2> "$OUT/$tag.err"
   else
     RR_LIB_PATH="$R/tools/ab/lib_$1.so" timeout -k 10 200 python bench.py --integrator dopri5 --n "$3" --steps 50 \

@@ -27,17 +27,17 @@ if has tests; then
 fi
 if has bench; then
   # the driver's protocol, with the CPU baselines and the SB3-facing legs
-  step bench_k20_1 500 $B --steps 20 --warmup 5 > "$OUT/bench_k20_1.json" 2> "$OUT/bench_k20_1.err"
+  step bench_k20_1 500 $B --full --steps 20 --warmup 5 > "$OUT/bench_k20_1.json" 2> "$OUT/bench_k20_1.err"
   cat "$OUT/bench_k20_1.json"
-  step bench_k20_2 300 $B --steps 20 --warmup 5 --no-cpu-baseline --no-sb3-legs > "$OUT/bench_k20_2.json" 2> "$OUT/bench_k20_2.err"
-  step bench_k2000 300 $B --no-cpu-baseline --no-sb3-legs > "$OUT/bench_k2000.json" 2> "$OUT/bench_k2000.err"
+  step bench_k20_2 300 $B --full --steps 20 --warmup 5 --no-cpu-baseline --no-sb3-legs > "$OUT/bench_k20_2.json" 2> "$OUT/bench_k20_2.err"
+  step bench_k2000 300 $B --full --no-cpu-baseline --no-sb3-legs > "$OUT/bench_k2000.json" 2> "$OUT/bench_k2000.err"
 fi
 if has dist; then
-  (export RR_BENCH_ONE_DEVICE=1 RR_BENCH_BACKEND=gloo; step bench_gpus2_gloo 400 $B --gpus 2 --steps 20 --warmup 5 > "$OUT/bench_gpus2_gloo.json" 2> "$OUT/bench_gpus2_gloo.err") || exit $?
+  (export RR_BENCH_ONE_DEVICE=1 RR_BENCH_BACKEND=gloo; step bench_gpus2_gloo 400 $B --full --gpus 2 --steps 20 --warmup 5 > "$OUT/bench_gpus2_gloo.json" 2> "$OUT/bench_gpus2_gloo.err") || exit $?
   cat "$OUT/bench_gpus2_gloo.json"
   # configs[3]'s launcher path at 4 ranks: the line's per_rank rows (every rank's wall / events figure)
-  (export RR_BENCH_ONE_DEVICE=1 RR_BENCH_BACKEND=gloo; step bench_gpus4_gloo 400 $B --gpus 4 --steps 20 --warmup 5 > "$OUT/bench_gpus4_gloo.json" 2> "$OUT/bench_gpus4_gloo.err") || exit $?
-  step bench_gather_w1 300 $B --gather-leg --steps 20 --warmup 5 --no-cpu-baseline --no-sb3-legs > "$OUT/bench_gather_w1.json" 2> "$OUT/bench_gather_w1.err"
+  (export RR_BENCH_ONE_DEVICE=1 RR_BENCH_BACKEND=gloo; step bench_gpus4_gloo 400 $B --full --gpus 4 --steps 20 --warmup 5 > "$OUT/bench_gpus4_gloo.json" 2> "$OUT/bench_gpus4_gloo.err") || exit $?
+  step bench_gather_w1 300 $B --full --gather-leg --steps 20 --warmup 5 --no-cpu-baseline --no-sb3-legs > "$OUT/bench_gather_w1.json" 2> "$OUT/bench_gather_w1.err"
 fi
 export TMPDIR=/tmp
 if has prof; then
@@ -63,7 +63,7 @@ if has pmc; then
 fi
 if has rollout; then
   # configs[4]: the collect rate + its roofline, the collect kernel under the tracer and its SQ counters
-  step rollout 400 $B --mode rollout --steps 320 > "$OUT/rollout.json" 2> "$OUT/rollout.err"
+  step rollout 400 $B --full --mode rollout --steps 320 > "$OUT/rollout.json" 2> "$OUT/rollout.err"
   cat "$OUT/rollout.json" | head -c 600; echo
   mkdir -p "$OUT/rp_rollout"
   (cd /tmp && step rp_rollout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rp_rollout" -o bench -- python "$R/bench.py" --mode rollout --steps 320 > "$OUT/rp_rollout/bench.json" 2> "$OUT/rp_rollout/bench.err") || exit $?
