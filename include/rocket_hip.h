@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define RR_ABI_VERSION 12
+#define RR_ABI_VERSION 13
 
 /* error codes */
 #define RR_OK 0
@@ -295,6 +295,18 @@ int rr_policy_pack(int obs_dim, int act_dim, int precision, const float* const* 
  *   (or NULL; the rollout buffer's obs[t]). The normal draws are counter-based on
  *   (seed, env_id_offset + i, *iter, t): `iter` is a device uint64 the caller advances once
  *   per rollout, so graph replays draw new noise. params 16-B aligned.
+ *   The noise key (32-bit arithmetic; mix32 = lowbias32; restated in tests/rollout_ref.py and
+ *   pinned element by element by tests/test_gpu_rollout_replay.py):
+ *     s   = splitmix64(seed)   one step on the host, as rr_seed's key words, so that the
+ *                              streams of two user seeds share nothing (raw seed words XORed
+ *                              into the key gave seed 1 the streams of seed 0 with envs e, e ^ 1
+ *                              swapped, and seed 2^32 those of seed 0 one iteration on)
+ *     key = mix32((uint32)(env_id_offset + i) ^ (uint32)s)
+ *     key = mix32(key ^ (uint32)*iter ^ (uint32)(s >> 32))
+ *     key = mix32(key ^ (uint32)(*iter >> 32) ^ t * 0x9E3779B9)
+ *   and for each pair of action components a = 0, 2, ..: k = key + a * 0x632BE5AB,
+ *     h1 = mix32(k), h2 = mix32(k ^ 0x68E31DA4), u1 = ((h1 >> 8) + 1) 2^-24 in (0, 1],
+ *     u2 = (h2 >> 8) 2^-24, (eps[a], eps[a + 1]) = sqrt(-2 ln u1) (cos, sin)(2 pi u2).
  *   If reward_out != NULL: reward_out[i] = prev_reward[i] + gamma * V(prev_term_obs[i])
  *   where prev_truncated[i] (the timeout bootstrap of step t-1; rr_step's outputs and
  *   rr_get_buffers' terminal_obs). If start_out != NULL: start_out[i] = done[i] (episode
@@ -315,7 +327,8 @@ int rr_policy_bootstrap(const float* params, int obs_dim, int act_dim, int preci
 /* One rollout step in ONE launch: rr_policy_act (without its previous-step bookkeeping) and
  * rr_step fused. For every env i of e: obs = state * normalizer^-1 (the obs rr_step /
  * rr_reset last produced) -> buf_obs [n][obs_dim]; a ~ N(mean, exp(log_std)) with the noise
- * key of rr_policy_act (seed, env id, *iter, t) -> buf_action [n][act_dim] (unclipped),
+ * key of rr_policy_act (splitmix64(seed), env_id_offset + i, *iter, t: the same draws,
+ * whatever the sharding) -> buf_action [n][act_dim] (unclipped),
  * buf_value, buf_log_prob; the env steps with clip(a, -1, 1) (auto-reset, TimeLimit, terminal
  * rows as rr_step); buf_reward[i] = reward + gamma * V(terminal obs) where truncated;
  * buf_start[i] = done[i] as passed in (the previous step's done flags, updated in place to
@@ -334,21 +347,25 @@ int rr_rollout_step(rr_env* e, const float* params, int precision, uint64_t seed
  * bootstrap and buffer writes, now into the [t] slices of [n_steps][n] buffers — with the env
  * state kept in registers between steps; then last_value[i] = V(post-step obs) (as
  * rr_policy_bootstrap), last_done[i] = last_start[i] = float(done[i]) and, when
- * buf_advantage / buf_return are given, the GAE scan of rr_gae(gamma, gae_lambda). Env outputs
+ * buf_advantage / buf_return are given, the GAE scan of rr_gae(gamma, gae_lambda) (fp64; the
+ * timeout bootstrap uses (float)gamma as rr_rollout_step does). Env outputs
  * (obs, reward, done, truncated, terms) are those of the last step. last_* / obs / truncated /
  * terms may be NULL. Bitwise the same results as n_steps rr_rollout_step launches +
  * rr_policy_bootstrap + rr_gae. RK4 / Euler envs. */
 int rr_rollout_collect(rr_env* e, const float* params, int precision, uint64_t seed, const uint64_t* iter,
-                       int n_steps, float gamma, float gae_lambda, float* buf_obs, float* buf_action,
+                       int n_steps, double gamma, double gae_lambda, float* buf_obs, float* buf_action,
                        float* buf_value, float* buf_log_prob, float* buf_start, float* buf_reward,
                        float* buf_advantage, float* buf_return, float* last_value, float* last_done,
                        float* last_start, float* obs, float* reward, uint8_t* done, uint8_t* truncated, float* terms,
                        void* stream);
 
 /* RolloutBuffer.compute_returns_and_advantage: rewards / values / starts [T][n] (starts[t]
- * = episode-start flag of step t), last_value / last_done [n] -> advantages, returns [T][n]. */
+ * = episode-start flag of step t), last_value / last_done [n] -> advantages, returns [T][n].
+ * The backward scan runs in fp64 (gamma, lam doubles since ABI 13) and each stored value is
+ * rounded to fp32 once: within half an fp32 ulp of the fp64 scan of the same inputs, where an
+ * fp32 scan is ~5e-5 off at |A| ~ 150 (tests/test_gpu_rollout_replay.py). */
 int rr_gae(int64_t T, int64_t n, const float* rewards, const float* values, const float* starts,
-           const float* last_value, const float* last_done, float gamma, float lam, float* advantages,
+           const float* last_value, const float* last_done, double gamma, double lam, float* advantages,
            float* returns, void* stream);
 
 /* ---- PPO minibatch gradient (the learner half of configs[4]) ----

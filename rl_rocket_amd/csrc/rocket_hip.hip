@@ -1520,15 +1520,19 @@ float floor_f(double d)  // largest float <= d
     return f;
 }
 
+// one splitmix64 step (host side): the user seed never reaches a kernel's key unmixed
+uint64_t splitmix64(uint64_t x)
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // 64-bit user seed -> the reset stream's four key words (splitmix64, host side)
 void seed_words(uint64_t seed, uint32_t* w)
 {
-    auto sm = [](uint64_t x) {
-        uint64_t z = x + 0x9E3779B97F4A7C15ull;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    };
+    const auto sm = splitmix64;
     const uint64_t a = sm(seed), b = sm(seed + 0x9E3779B97F4A7C15ull);
     w[0] = (uint32_t)a;
     w[1] = (uint32_t)(a >> 32);
@@ -2423,7 +2427,10 @@ int rr_policy_act(const float* params, int obs_dim, int act_dim, int precision, 
     if (((uintptr_t)params & 15) != 0) return fail(RR_EINVAL, "rr_policy_act: params must be 16-B aligned");
     const dim3 grid((unsigned)((n + pol::kEnvsPerBlock - 1) / pol::kEnvsPerBlock)), block(pol::kThreads);
     hipStream_t s = (hipStream_t)stream;
-    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
+    // the noise key's seed words: splitmix64 of the user seed (raw seed words XORed into the key
+    // made seed 1 give env e the stream seed 0 gives env e ^ 1, and seed 2^32 that of iteration + 1)
+    const uint64_t mixed = splitmix64(seed);
+    const uint32_t lo = (uint32_t)mixed, hi = (uint32_t)(mixed >> 32);
     const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto c) {
         using C = decltype(c);
         hipLaunchKernelGGL((policy_act_kernel<C::OBS, C::ACT, C::PREC>), grid, block, 0, s, params, n, env_id_offset,
@@ -2472,8 +2479,9 @@ int launch_rollout(rr_env* e, const char* who, bool multi, const float* params, 
         return fail(RR_EINVAL, std::string(who) + ": RR_INT_DOPRI5 envs step through rr_policy_act + rr_step");
     io.params = params;
     io.iter = iter;
-    io.seed_lo = (uint32_t)seed;
-    io.seed_hi = (uint32_t)(seed >> 32);
+    const uint64_t mixed = splitmix64(seed);  // as rr_policy_act: the same noise key
+    io.seed_lo = (uint32_t)mixed;
+    io.seed_hi = (uint32_t)(mixed >> 32);
     io.obs_vec_ok = ((uintptr_t)io.obs & 15u) == 0;
     io.buf_obs_vec_ok = ((uintptr_t)io.buf_obs & 15u) == 0;
     const Bufs b = bufs_of(e);
@@ -2545,7 +2553,7 @@ int rr_rollout_step(rr_env* e, const float* params, int precision, uint64_t seed
 }
 
 int rr_rollout_collect(rr_env* e, const float* params, int precision, uint64_t seed, const uint64_t* iter,
-                       int n_steps, float gamma, float gae_lambda, float* buf_obs, float* buf_action,
+                       int n_steps, double gamma, double gae_lambda, float* buf_obs, float* buf_action,
                        float* buf_value, float* buf_log_prob, float* buf_start, float* buf_reward,
                        float* buf_advantage, float* buf_return, float* last_value, float* last_done,
                        float* last_start, float* obs, float* reward, uint8_t* done, uint8_t* truncated, float* terms,
@@ -2574,13 +2582,14 @@ int rr_rollout_collect(rr_env* e, const float* params, int precision, uint64_t s
     io.terms = terms;
     io.t = 0;
     io.T = (uint32_t)n_steps;
-    io.gamma = gamma;
+    io.gamma = (float)gamma;  // the timeout bootstrap, fp32 as rr_rollout_step's
+    io.gamma64 = gamma;
     io.lam = gae_lambda;
     return launch_rollout(e, "rr_rollout_collect", true, params, precision, seed, iter, io, stream);
 }
 
 int rr_gae(int64_t T, int64_t n, const float* rewards, const float* values, const float* starts,
-           const float* last_value, const float* last_done, float gamma, float lam, float* advantages,
+           const float* last_value, const float* last_done, double gamma, double lam, float* advantages,
            float* returns, void* stream)
 {
     if (!rewards || !values || !starts || !last_value || !last_done || !advantages || !returns || T <= 0 || n <= 0)

@@ -600,10 +600,13 @@ __device__ __forceinline__ void bootstrap_wave(const float* sp, float* so2, cons
 }
 
 // SB3 1.6 RolloutBuffer.compute_returns_and_advantage for env e of a [T][n] rollout
-// (rr_gae and the one-launch collect share it, so their results are bitwise equal).
+// (rr_gae and the one-launch collect share it, so their results are bitwise equal). The scan
+// runs in fp64 and rounds each stored advantage / return once: terminal rewards of +-60 take |A|
+// past 128, where an fp32 scan's roundings add up to ~5e-5 over 16 steps (gamma, lambda as doubles
+// for the same reason: 0.99f is 0.99 + 9.5e-9).
 __device__ __forceinline__ void gae_env(int64_t T, int64_t n, int64_t e, const float* __restrict__ rewards,
                                         const float* __restrict__ values, const float* __restrict__ starts,
-                                        float last_value, float last_done, float gamma, float lam,
+                                        float last_value, float last_done, double gamma, double lam,
                                         float* __restrict__ adv, float* __restrict__ ret)
 {
     // backward over t in chunks of kC steps whose loads are all issued before the chunk's scan:
@@ -611,8 +614,10 @@ __device__ __forceinline__ void gae_env(int64_t T, int64_t n, int64_t e, const f
     // previous step's adv / ret stores on their own; in the collect kernel they read back what the
     // step loop just wrote, so each was a full write-then-read round trip)
     constexpr int kC = 16;
-    float last = 0.0f;
-    float next_v = last_value, next_nt = 1.0f - last_done;
+    // the flags are exactly 0 / 1: (1 - start) as a select of the coefficient, two fp64 FMAs per step
+    const double gl = gamma * lam;
+    double last = 0.0;
+    double next_v = last_value, next_g = last_done != 0.0f ? 0.0 : gamma, next_gl = last_done != 0.0f ? 0.0 : gl;
     for (int64_t t1 = T; t1 > 0; t1 -= kC) {
         const int c = t1 < kC ? (int)t1 : kC;
         float rw[kC], vl[kC], st[kC];
@@ -628,13 +633,13 @@ __device__ __forceinline__ void gae_env(int64_t T, int64_t n, int64_t e, const f
         for (int j = 0; j < kC; ++j)
             if (j < c) {
                 const int64_t k = (t1 - 1 - j) * n + e;
-                const float v = vl[j];
-                const float delta = rw[j] + gamma * next_v * next_nt - v;
-                last = delta + gamma * lam * next_nt * last;
-                adv[k] = last;
-                ret[k] = last + v;
+                const double v = vl[j];
+                last = fma(next_gl, last, fma(next_g, next_v, (double)rw[j] - v));
+                adv[k] = (float)last;
+                ret[k] = (float)(last + v);
                 next_v = v;
-                next_nt = 1.0f - st[j];
+                next_g = st[j] != 0.0f ? 0.0 : gamma;
+                next_gl = st[j] != 0.0f ? 0.0 : gl;
             }
     }
 }
@@ -882,7 +887,7 @@ __global__ __launch_bounds__(kBlock) void gae_kernel(int64_t T, int64_t n, const
                                                      const float* __restrict__ values,
                                                      const float* __restrict__ starts,
                                                      const float* __restrict__ last_value,
-                                                     const float* __restrict__ last_done, float gamma, float lam,
+                                                     const float* __restrict__ last_done, double gamma, double lam,
                                                      float* __restrict__ adv, float* __restrict__ ret)
 {
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;

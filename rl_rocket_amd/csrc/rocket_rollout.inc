@@ -42,7 +42,7 @@ struct RolloutIO {
     int32_t obs_vec_ok, buf_obs_vec_ok;
     // rr_rollout_collect only (MULTI): steps per launch and the end-of-rollout outputs
     uint32_t T;
-    float lam;
+    double gamma64, lam;        // GAE coefficients (the scan runs in fp64; gamma above is the bootstrap's)
     float* buf_adv;             // [T][n] or nullptr (no GAE)
     float* buf_ret;             // [T][n]
     float* last_value;          // [n] V(obs after the last step) or nullptr
@@ -496,7 +496,7 @@ __global__ __launch_bounds__(rol::Shape<NTW>::kThreads) void rollout_step_kernel
             if (io.last_done) io.last_done[i] = ld;
             if (io.last_start) io.last_start[i] = ld;
             if (io.buf_adv)
-                pol::gae_env(T, n, i, io.buf_rew, io.buf_val, io.buf_start, lv, ld, io.gamma, io.lam, io.buf_adv,
+                pol::gae_env(T, n, i, io.buf_rew, io.buf_val, io.buf_start, lv, ld, io.gamma64, io.lam, io.buf_adv,
                              io.buf_ret);
         }
         RR_ST(14);

@@ -222,5 +222,5 @@ def test_abi_8_to_12_entry_points_refuse_bad_arguments_before_any_hip_call():
     refused(update(nxt=fake, next_batch=1), "rr_ppo_update")
     refused(update(nxt=fake, next_batch=65), "rr_ppo_update")  # longer than this minibatch
     # rollouts / GAE (kept from ABI 3-7)
-    refused(lib.rr_gae(16, 0, fake, fake, fake, fake, fake, ctypes.c_float(0.99), ctypes.c_float(0.95), fake, fake,
+    refused(lib.rr_gae(16, 0, fake, fake, fake, fake, fake, ctypes.c_double(0.99), ctypes.c_double(0.95), fake, fake,
                        None), "rr_gae")
