@@ -10,19 +10,17 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc", "rocket_hip.hip")
-# the exact-mode kernels' translation unit (rocket_hip.hip again under RR_TU_EXACT), compiled with
+# the exact-mode kernels' translation unit (rocket_device.h + rocket_dopri5.inc), compiled with
 # a register-pressure-first scheduler: with the fast kernels' setting the 6DOF exact kernel spilled
 # 33 VGPRs to scratch at one wave per SIMD (r03e), with it none
 SRC_EXACT = os.path.join(HERE, "csrc", "rocket_exact.hip")
 EXACT_FLAGS = ["-mllvm", "-amdgpu-schedule-metric-bias=100"]
-# the rollout collect and PPO learner kernels' translation unit (rocket_hip.hip under RR_TU_COLLECT),
+# the rollout collect and PPO learner kernels' translation unit (rocket_device.h + the policy /
+# rollout / ppo includes),
 # with the MFMA accumulators in VGPRs: no v_accvgpr_read per tanh input (5.5 % faster collect,
 # round 4; the learner's minibatch 3 % faster, round 6)
 SRC_COLLECT = os.path.join(HERE, "csrc", "rocket_collect.hip")
 COLLECT_FLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
-DEPS = [os.path.join(HERE, "csrc", f) for f in ("rocket_dopri5.inc", "rocket_policy.inc", "rocket_rollout.inc", "rocket_ppo.inc",
-                                                 "rocket_exact.hip", "rocket_collect.hip",
-                                                 "rocket_stamps.h")]
 HEADER = os.path.join(ROOT, "include", "rocket_hip.h")
 OUT = os.path.join(HERE, "librocket_hip.so")
 # benchmark-only helper (not part of the product ABI): bench.py's event-timed direct-launch region
@@ -57,6 +55,14 @@ def command(resource_usage=False, out=OUT, defines=(), extra=(), src=SRC, compil
     return cmd
 
 
+def sources():
+    """Every file the three translation units are compiled from: all of csrc/ and the C-ABI header,
+    sorted (tests/test_build_sources.py checks that the #include graph stays inside this list)."""
+    csrc = os.path.join(HERE, "csrc")
+    return sorted([os.path.join(csrc, f) for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))]
+                  + [HEADER])
+
+
 def source_hash():
     """sha256 of everything that determines the kernels' code: the HIP sources, the C-ABI
     header and the compile command (tools/pmc_traffic.py stamps its output with it; bench.py
@@ -64,7 +70,7 @@ def source_hash():
     import hashlib
 
     h = hashlib.sha256()
-    for path in [SRC, HEADER] + DEPS:
+    for path in sources():
         with open(path, "rb") as f:
             h.update(f.read())
     for cmd in commands():
@@ -181,7 +187,7 @@ def up_to_date():
     if not os.path.exists(OUT):
         return False
     t = os.path.getmtime(OUT)
-    return all(os.path.getmtime(p) <= t for p in [SRC, HEADER, __file__] + DEPS)
+    return all(os.path.getmtime(p) <= t for p in sources() + [__file__])
 
 
 def build(force=False, resource_usage=False, verbose=True):

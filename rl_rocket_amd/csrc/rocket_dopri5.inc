@@ -26,26 +26,15 @@
 // (rocket_env.py:690-719, 825-859, 986-1014, 1036-1061 / :150-247, 431-476) in the
 // reference's own precision (float32 state, float64 arithmetic), not the fp32 tricks
 // of the fast kernel.
+//
+// Included by rocket_exact.hip only, between `#pragma clang fp contract(off)` and `(fast)`, after
+// rocket_device.h (which must stay outside that pragma).
+#pragma once
 
-// Host-derived fp64 constants of the exact mode.
-struct XParams {
-    double dt;
-    double dt_milli;          // rint(dt * 1000) when dt has <= 3 decimals (clock exact), else 0
-    double norm[RR_MAX_STATE];
-    double lo[3], hi[3];      // bounds as rr_params
-    double max_gimbal, max_thrust;
-    double alfa, beta, eta, gamma, delta, kappa, xi;
-    double waypoint, landing_radius, max_velocity;
-    double att_limit[3], land_att_limit[3], omega_lim[3];
-    int32_t clamp_h0;
-    // the attitude tests without inverse trig (finish6; make_xparams): axes 0, 2 (atan2) cos of the
-    // limit, axis 1 (asin) its sin; bit k of att_never / land_always: the test is constant
-    double att_c[3], land_c[3];
-    uint32_t att_never, land_always;
-    uint32_t att_always, land_never;  // L < 0: |e| > L always; M <= 0: |e| < M never
-};
+#include "rocket_device.h"
 
-#ifdef RR_TU_EXACT  // the solver and its kernels: the exact translation unit only (rocket_exact.hip)
+namespace {
+
 namespace dp {
 
 constexpr double kG0 = 9.81, kIsp = 360.0;
@@ -783,19 +772,4 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(LEAN ? 2
     RR_STAMPS_WRITE(io.reward, i, (uint32_t)(threadIdx.x & (kWave - 1)), true, false);
 }
 
-#endif  // RR_TU_EXACT
-
-#if !defined(RR_TU_EXACT) && !defined(RR_TU_COLLECT)
-// fp32 <-> fp64 state planes (rr_set_state / rr_set_state64 / rr_get_state64)
-__global__ __launch_bounds__(kBlock) void widen_kernel(const float* src, double* dst, int64_t count)
-{
-    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (k < count) dst[k] = (double)src[k];
-}
-
-__global__ __launch_bounds__(kBlock) void narrow_kernel(const double* src, float* dst, int64_t count)
-{
-    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (k < count) dst[k] = (float)src[k];
-}
-#endif  // !RR_TU_EXACT && !RR_TU_COLLECT
+}  // namespace

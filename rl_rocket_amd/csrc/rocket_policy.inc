@@ -37,6 +37,13 @@
 // pre-scaled); the 2^-16 folds into the tanh's exponent constant. Same fragment layout as bf16,
 // weights packed as [hi, lo] planes. Products carry ~2^-21 relative error against fp32's 2^-24,
 // at 3 x 32 instead of 8 x 64 MFMA cycles per 16 k.
+//
+// The including translation unit defines RR_POL_PREFETCH_A (0 or 1, see kPolPrefetchA) first.
+#pragma once
+
+#include "rocket_device.h"
+
+namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -45,12 +52,12 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // layer-2 A fragments read a group ahead (a second register set) in the collect kernels' translation
 // unit (rocket_collect.hip: MFMA accumulators in VGPRs, one wave per SIMD); the main translation
 // unit's per-step rollout kernels keep one set: there the extra registers would cost the split-fp16
-// kernel its second wave per SIMD (248 -> 268 registers)
-#if defined(RR_TU_COLLECT)
-constexpr bool kPolPrefetchA = true;
-#else
-constexpr bool kPolPrefetchA = false;
+// kernel its second wave per SIMD (248 -> 268 registers). The translation unit chooses:
+// rocket_hip.hip defines RR_POL_PREFETCH_A 0, rocket_collect.hip 1.
+#ifndef RR_POL_PREFETCH_A
+#error "define RR_POL_PREFETCH_A (0: one A fragment set, 1: read a group ahead) before including rocket_policy.inc"
 #endif
+constexpr bool kPolPrefetchA = RR_POL_PREFETCH_A;
 
 // packed-f32 tanh (v_pk_mul/add/fma_f32 on register pairs) on the fp32 and bf16 towers (bit p set
 // for precision p; the split-fp16 path has its own scaled tanh)
@@ -880,18 +887,4 @@ __global__ __launch_bounds__(256) void policy_pack_kernel(PolSrc src, float* __r
     dst[k] = v;
 }
 
-#ifndef RR_TU_COLLECT  // the collect TU (rocket_collect.hip) holds the collect kernel only
-// SB3 RolloutBuffer.compute_returns_and_advantage on device: one thread per env scans t
-// backwards. rewards/values/starts [T][n]; starts[t] = episode start flag of step t.
-__global__ __launch_bounds__(kBlock) void gae_kernel(int64_t T, int64_t n, const float* __restrict__ rewards,
-                                                     const float* __restrict__ values,
-                                                     const float* __restrict__ starts,
-                                                     const float* __restrict__ last_value,
-                                                     const float* __restrict__ last_done, double gamma, double lam,
-                                                     float* __restrict__ adv, float* __restrict__ ret)
-{
-    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (e >= n) return;
-    pol::gae_env(T, n, e, rewards, values, starts, last_value[e], last_done[e], gamma, lam, adv, ret);
-}
-#endif  // RR_TU_COLLECT
+}  // namespace

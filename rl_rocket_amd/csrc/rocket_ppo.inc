@@ -34,8 +34,17 @@
 // Then clip_grad_norm_ + Adam: adam_norm_kernel + adam_step_kernel (rr_clip_adam), or, for a whole
 // minibatch step in one call (rr_ppo_update), the finish also sums the squared gradients and
 // adam_chain_kernel steps, repacks the towers and sums the next minibatch's statistics.
-// The types are shared by both translation units; the kernels are compiled and launched in the
-// collect TU (rocket_collect.hip, rrc_launch_learner).
+// The types and the kernel templates are here for both translation units that include this file;
+// the kernels are instantiated and launched in the collect TU (rocket_collect.hip,
+// rrc_launch_learner), which also defines adam_norm_kernel / adam_step_kernel.
+#pragma once
+
+#include <type_traits>
+
+#include "rocket_device.h"
+#include "rocket_policy.inc"
+
+namespace {
 
 namespace ppo {
 
@@ -766,55 +775,6 @@ __device__ __forceinline__ float block_sum(float v, float* red)
     return tot;
 }
 
-#ifdef RR_TU_COLLECT  // the learner's kernels are compiled in the collect TU (rocket_collect.hip)
-// work[b] = sum of g^2 over block b's elements; work[gridDim.x] = the new step count
-__global__ __launch_bounds__(kAdamThreads) void adam_norm_kernel(AdamList A, float* __restrict__ work)
-{
-    __shared__ float red[kAdamThreads / kWave];
-    const int64_t e = (int64_t)blockIdx.x * kAdamThreads + threadIdx.x;
-    float g = 0.0f;
-    if (e < A.start[A.n]) {
-        const int t = adam_tensor_of(A, e);
-        g = A.grad[t][e - A.start[t]];
-    }
-    const float tot = block_sum<kAdamThreads>(g * g, red);
-    if (threadIdx.x == 0) {
-        work[blockIdx.x] = tot;
-        if (blockIdx.x == 0) work[gridDim.x] = *A.step[0] + 1.0f;
-    }
-}
-
-__global__ __launch_bounds__(kAdamThreads) void adam_step_kernel(AdamList A, const float* __restrict__ work,
-                                                                 float max_norm, const float* __restrict__ lr_p,
-                                                                 float beta1, float beta2, float w1, float w2, float eps)
-{
-    __shared__ float red[kAdamThreads / kWave];
-    const int nb = gridDim.x;
-    float part = 0.0f;
-    for (int b = threadIdx.x; b < nb; b += kAdamThreads) part += work[b];
-    const float tot = block_sum<kAdamThreads>(part, red);
-    const float step = work[nb], lr = *lr_p;
-    const float coef = max_norm > 0.0f ? fminf(max_norm / (sqrtf(tot) + 1e-6f), 1.0f) : 1.0f;
-    const float bc1 = 1.0f - powf(beta1, step), bc2 = 1.0f - powf(beta2, step);
-    const float sneg = -(1.0f / (bc1 / lr));
-    const float d = sqrtf(bc2) * sneg, eos = 1.0f / (sneg / eps);
-    const int64_t e = (int64_t)blockIdx.x * kAdamThreads + threadIdx.x;
-    if (e < A.start[A.n]) {
-        const int t = adam_tensor_of(A, e);
-        const int64_t k = e - A.start[t];
-        float *p = A.param[t], *gp = A.grad[t], *m = A.exp_avg[t], *v = A.exp_avg_sq[t];
-        const float g = gp[k] * coef;
-        gp[k] = g;
-        const float mk = m[k] + w1 * (g - m[k]);
-        const float vk = v[k] * beta2 + (w2 * g) * g;
-        m[k] = mk;
-        v[k] = vk;
-        p[k] = p[k] + mk / (sqrtf(vk) / d + eos);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < A.n) *A.step[threadIdx.x] = step;
-}
-#endif  // RR_TU_COLLECT
-
 // rr_ppo_update's optimizer launch: the clip + Adam step of adam_step_kernel over the 13 policy
 // tensors in rr_ppo_grad's order, with the squared-gradient sums and the step count from
 // ppo_finish_kernel (normw[0 .. n_norm), normw[n_norm]); each updated parameter also goes to its
@@ -845,6 +805,7 @@ struct PpoLaunch {
     int obs_dim, nwg, nbp, op;  // op: 0 rr_ppo_grad, 1 rr_ppo_update, 2 rr_clip_adam
     uint32_t flags;
 };
+static_assert(std::is_trivially_copyable_v<PpoLaunch>, "PpoLaunch crosses TUs by memcpy (rrc_launch_learner)");
 
 // Element k of policy tensor t (rr_ppo_grad order) into the packed images (two towers of Pack::SIZE).
 template <int OBS, int ACT>
@@ -956,3 +917,5 @@ __global__ __launch_bounds__(kAdamThreads) void adam_chain_kernel(AdamList A, co
     }
     if (blockIdx.x == 0 && threadIdx.x < A.n) *A.step[threadIdx.x] = step;
 }
+
+}  // namespace

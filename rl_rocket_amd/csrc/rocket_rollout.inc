@@ -23,6 +23,15 @@
 // env's GAE scan (the code of rr_policy_bootstrap and rr_gae). Bitwise the same rollout as T
 // rr_rollout_step launches + rr_policy_bootstrap + rr_gae (tests/test_gpu_rollout.py).
 
+#pragma once
+
+#include <type_traits>
+
+#include "rocket_device.h"
+#include "rocket_policy.inc"
+
+namespace {
+
 struct RolloutIO {
     const float* params;        // packed policy (rr_policy_layout / rr_policy_pack), 16-B aligned
     const uint64_t* iter;       // device rollout counter (noise key)
@@ -49,6 +58,7 @@ struct RolloutIO {
     float* last_done;           // [n] float(done of the last step) or nullptr
     float* last_start;          // [n] same values (SB3 _last_episode_starts) or nullptr
 };
+static_assert(std::is_trivially_copyable_v<RolloutIO>, "RolloutIO crosses TUs by memcpy (rrc_launch_collect)");
 
 namespace rol {
 // NTW 32-env MFMA column tiles per wave: 2 = 64 envs per wave, 4 waves per workgroup (the
@@ -503,3 +513,5 @@ __global__ __launch_bounds__(rol::Shape<NTW>::kThreads) void rollout_step_kernel
         RR_ACC_WRITE(io.last_value, wave_base, lane, live && wave_base + lane < n && io.last_value);
     }
 }
+
+}  // namespace
