@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define RR_ABI_VERSION 13
+#define RR_ABI_VERSION 14
 
 /* error codes */
 #define RR_OK 0
@@ -358,6 +358,51 @@ int rr_rollout_collect(rr_env* e, const float* params, int precision, uint64_t s
                        float* buf_advantage, float* buf_return, float* last_value, float* last_done,
                        float* last_start, float* obs, float* reward, uint8_t* done, uint8_t* truncated, float* terms,
                        void* stream);
+
+/* ---- On-device deterministic policy evaluation (ABI 14) ----
+ * Replaces stable_baselines3 EvalCallback / evaluate_policy(deterministic=True) on an
+ * EpisodeAnalyzer-wrapped env (reference main_6DOF.py:60-103: EvalCallback(eval_env, n_eval_episodes=5,
+ * deterministic=True); wrappers.py:189-235: ep_statistic/landing_success, ep_statistic/used_mass,
+ * final_errors/<state name>): every env of the handle runs n_episodes whole episodes under the
+ * policy's MEAN action in ONE launch. A step is rr_rollout_step's with the noise removed: obs =
+ * state * normalizer^-1, the pi tower and action heads of the packed policy (no value tower, no
+ * sampling), the env steps with clip(mean, -1, 1), reward, TimeLimit and auto-reset (the reset
+ * stream's draw for the env's counter word) as rr_step; the env state, counter word and running
+ * return stay in registers between steps and nothing is written per step. Bitwise the episodes
+ * rr_rollout_step runs where exp(log_std) * noise is absorbed by the mean (tests/test_gpu_eval.py).
+ *   - Episode 0 of env i starts from the handle's CURRENT state (reset first for whole episodes;
+ *     its return continues the running Monitor return under RR_FLAG_EPISODE_STATS, else starts at
+ *     0, and its used mass counts from the state at the call).
+ *   - When env i ends an episode (done or TimeLimit) row [ep][i] of the given planes is written;
+ *     after its n_episodes-th it rests at the first state of a fresh episode: elapsed 0, episode
+ *     number advanced by n_episodes, running return 0.
+ *   - max_steps caps the steps of every env (<= 0: n_episodes * max_episode_steps, which always
+ *     suffices); rows of episodes not completed by then are left untouched, episodes[i] counts the
+ *     completed ones and the env rests mid-episode, exactly as after that many steps.
+ *   - obs (or NULL) receives the post-call observation of every env.
+ * The done list of the handle (rr_fetch_done / rr_copy_terminal / rr_get_buffers' done_bits and
+ * terminal_*) is NOT touched: it still refers to the last rr_step / rollout launch.
+ * RR_EINVAL: a handle without RR_FLAG_AUTO_RESET, RR_INT_DOPRI5, n_episodes < 1, no TimeLimit and
+ * max_steps <= 0 (nothing bounds the launch), out or out->episodes NULL, params NULL or not 16-B
+ * aligned, a precision that is not RR_POLICY_*. Asynchronous on `stream`, capturable in a hipGraph,
+ * ordered for rr_seed like the handle's other launches. */
+#define RR_EVAL_EVENT     0x01  /* ended on the ground event (solve_ivp status 1) */
+#define RR_EVAL_BOUNDS    0x02  /* bounds violation */
+#define RR_EVAL_TRUNCATED 0x04  /* TimeLimit */
+#define RR_EVAL_NONFINITE 0x08  /* status -1 */
+#define RR_EVAL_LANDED    0x10  /* the terminal step's rew_goal term != 0 (ep_statistic/landing_success) */
+
+typedef struct rr_eval_out {      /* device pointers; planes are [n_episodes][n]; any but `episodes` may be NULL */
+    int32_t* episodes;            /* [n] episodes completed by env i (<= n_episodes) */
+    float*   ep_return;           /* sum of raw env rewards, fp32, step order */
+    int32_t* ep_length;
+    uint8_t* flags;               /* RR_EVAL_* */
+    float*   used_mass;           /* mass at the episode's first state - mass at its terminal state */
+    float*   final_state;         /* [n_episodes][state_dim][n]: the terminal (pre-reset) state, un-normalised */
+} rr_eval_out;
+
+int rr_policy_evaluate(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
+                       const rr_eval_out* out, float* obs /* [n][state_dim] or NULL */, void* stream);
 
 /* RolloutBuffer.compute_returns_and_advantage: rewards / values / starts [T][n] (starts[t]
  * = episode-start flag of step t), last_value / last_done [n] -> advantages, returns [T][n].

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RR_LIB_PATH") or os.path.join(HERE, "librocket_hip.so")  # override: diagnostics only
 HEADER = os.path.join(os.path.dirname(HERE), "include", "rocket_hip.h")
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 RR_OK, RR_EINVAL, RR_EHIP, RR_ENOMEM = 0, -1, -2, -3
 RR_MODEL_3DOF, RR_MODEL_6DOF = 3, 6
@@ -27,6 +27,7 @@ RR_FLAG_SCIPY_H0_CLAMP = 0x10
 RR_FLAG_HOST_STATE = 0x20
 RR_MAX_STATE = 14
 RR_POLICY_FP32, RR_POLICY_BF16, RR_POLICY_FP16X3 = 0, 1, 2
+RR_EVAL_EVENT, RR_EVAL_BOUNDS, RR_EVAL_TRUNCATED, RR_EVAL_NONFINITE, RR_EVAL_LANDED = 0x01, 0x02, 0x04, 0x08, 0x10
 
 _d3 = ctypes.c_double * 3
 _f14 = ctypes.c_float * RR_MAX_STATE
@@ -80,6 +81,19 @@ class RrBuffers(ctypes.Structure):
     ]
 
 
+class RrEvalOut(ctypes.Structure):
+    """Mirror of ``rr_eval_out`` (device pointers; any but ``episodes`` may be NULL)."""
+
+    _fields_ = [
+        ("episodes", ctypes.c_void_p),
+        ("ep_return", ctypes.c_void_p),
+        ("ep_length", ctypes.c_void_p),
+        ("flags", ctypes.c_void_p),
+        ("used_mass", ctypes.c_void_p),
+        ("final_state", ctypes.c_void_p),
+    ]
+
+
 # symbol -> (restype, argtypes); the test suite checks this against include/rocket_hip.h
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -120,6 +134,8 @@ SIGNATURES = {
                                        _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rr_rollout_collect": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_uint64, _P, ctypes.c_int, ctypes.c_double,
                                           ctypes.c_double] + [_P] * 17),
+    "rr_policy_evaluate": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                          ctypes.POINTER(RrEvalOut), _P, _P]),
     "rr_gae": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P,
                               _P, _P]),
     "rr_clip_adam_workspace_size": (ctypes.c_int, [ctypes.c_int64, _P]),

@@ -1,5 +1,7 @@
 // rocket_collect.hip — the third translation unit of librocket_hip.so: the rollout collect kernels
-// (rollout_step_kernel<..., MULTI = true>, rocket_rollout.inc: rr_rollout_collect) and the PPO
+// (rollout_step_kernel<..., MULTI = true>, rocket_rollout.inc: rr_rollout_collect), the evaluation
+// kernels (eval_kernel, rocket_eval.inc: rr_policy_evaluate, the collect's loop without its value
+// tower, launched through rrc_launch_eval) and the PPO
 // learner's kernels (rocket_ppo.inc: rr_ppo_grad / rr_ppo_update / rr_clip_adam, launched through
 // rrc_launch_learner), compiled with their own code-generation setting (rl_rocket_amd/build.py
 // COLLECT_FLAGS: -amdgpu-mfma-vgpr-form, the MFMA accumulators in VGPRs) without touching the other
@@ -17,6 +19,7 @@
 #define RR_POL_PREFETCH_A 1
 #include "rocket_policy.inc"
 #include "rocket_rollout.inc"
+#include "rocket_eval.inc"
 #include "rocket_ppo.inc"
 
 namespace {
@@ -101,6 +104,36 @@ extern "C" int rrc_launch_collect(int model, int integ, int prec, unsigned grid,
     else RR_COLLECT_P(3, RR_INT_EULER);
 #undef RR_COLLECT_P
 #undef RR_COLLECT
+    return (int)hipGetLastError();
+}
+
+// rr_policy_evaluate's launch (declared in rocket_device.h): eval_kernel<MODEL, INTEG, PREC>, the
+// collect's grid and workgroup. io points to the EvalIO of the calling TU.
+extern "C" int rrc_launch_eval(int model, int integ, int prec, unsigned grid, float* state, uint32_t n, uint32_t mode,
+                               const void* kp, const void* bufs, const void* io, void* stream)
+{
+    KParams p;
+    Bufs b;
+    EvalIO o;
+    std::memcpy(&p, kp, sizeof(KParams));
+    std::memcpy(&b, bufs, sizeof(Bufs));
+    std::memcpy(&o, io, sizeof(EvalIO));
+    hipStream_t s = (hipStream_t)stream;
+#define RR_EVAL(M, I, PR) \
+    hipLaunchKernelGGL((eval_kernel<M, I, PR>), dim3(grid), dim3(rol::Shape<2>::kThreads), 0, s, state, n, mode, p, b, o)
+#define RR_EVAL_P(M, I)                      \
+    do {                                     \
+        if (prec == 1) RR_EVAL(M, I, 1);     \
+        else if (prec == 2) RR_EVAL(M, I, 2); \
+        else RR_EVAL(M, I, 0);               \
+    } while (0)
+    const bool euler = integ == RR_INT_EULER;
+    if (model == RR_MODEL_6DOF && !euler) RR_EVAL_P(6, RR_INT_RK4);
+    else if (model == RR_MODEL_6DOF) RR_EVAL_P(6, RR_INT_EULER);
+    else if (!euler) RR_EVAL_P(3, RR_INT_RK4);
+    else RR_EVAL_P(3, RR_INT_EULER);
+#undef RR_EVAL_P
+#undef RR_EVAL
     return (int)hipGetLastError();
 }
 

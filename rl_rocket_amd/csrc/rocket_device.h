@@ -1096,8 +1096,8 @@ static_assert(std::is_trivially_copyable_v<StepIO>, "StepIO crosses TUs by memcp
 // The hidden entry points (not part of the C-ABI) through which the main translation unit launches
 // the kernels compiled in the other two. Defined in rocket_exact.hip / rocket_collect.hip; the
 // main TU adds weak stand-ins, so that a library built from rocket_hip.hip alone still loads.
-// xp / kp / bufs / io / launch point to the caller's XParams / KParams / Bufs / StepIO or RolloutIO /
-// PpoLaunch.
+// xp / kp / bufs / io / launch point to the caller's XParams / KParams / Bufs / StepIO, RolloutIO or
+// EvalIO / PpoLaunch.
 extern "C" {
 __attribute__((visibility("hidden"))) int rrx_launch_exact(int model, int variant, const void* xp, const void* bufs,
                                                            const void* io, double* state64, unsigned grid,
@@ -1105,5 +1105,8 @@ __attribute__((visibility("hidden"))) int rrx_launch_exact(int model, int varian
 __attribute__((visibility("hidden"))) int rrc_launch_collect(int model, int integ, int prec, unsigned grid,
                                                              float* state, uint32_t n, uint32_t mode, const void* kp,
                                                              const void* bufs, const void* io, void* stream);
+__attribute__((visibility("hidden"))) int rrc_launch_eval(int model, int integ, int prec, unsigned grid, float* state,
+                                                          uint32_t n, uint32_t mode, const void* kp,
+                                                          const void* bufs, const void* io, void* stream);
 __attribute__((visibility("hidden"))) int rrc_launch_learner(const void* launch, void* stream);
 }

@@ -36,6 +36,7 @@
 #define RR_POL_PREFETCH_A 0
 #include "rocket_policy.inc"
 #include "rocket_rollout.inc"
+#include "rocket_eval.inc"
 // PPO learner (loss + backward of the MlpPolicy on fp32 MFMA, clip + Adam): its types here, its
 // kernels compiled in and launched from the collect TU (rrc_launch_learner)
 #include "rocket_ppo.inc"
@@ -326,7 +327,7 @@ __global__ __launch_bounds__(kBlock) void narrow_kernel(const double* src, float
 
 // defined by the exact / collect translation units (declared in rocket_device.h); these weak
 // stand-ins (a library built from this file alone, e.g. a tools/ A/B variant) make RR_INT_DOPRI5
-// steps, rr_rollout_collect and the learner fail loudly instead of failing to load
+// steps, rr_rollout_collect, rr_policy_evaluate and the learner fail loudly instead of failing to load
 extern "C" __attribute__((weak, visibility("hidden"))) int rrx_launch_exact(int, int, const void*, const void*,
                                                                           const void*, double*, unsigned, void*)
 {
@@ -335,6 +336,12 @@ extern "C" __attribute__((weak, visibility("hidden"))) int rrx_launch_exact(int,
 extern "C" __attribute__((weak, visibility("hidden"))) int rrc_launch_collect(int, int, int, unsigned, float*,
                                                                             uint32_t, uint32_t, const void*,
                                                                             const void*, const void*, void*)
+{
+    return (int)hipErrorInvalidDeviceFunction;
+}
+extern "C" __attribute__((weak, visibility("hidden"))) int rrc_launch_eval(int, int, int, unsigned, float*, uint32_t,
+                                                                         uint32_t, const void*, const void*,
+                                                                         const void*, void*)
 {
     return (int)hipErrorInvalidDeviceFunction;
 }
@@ -1440,6 +1447,49 @@ int rr_rollout_collect(rr_env* e, const float* params, int precision, uint64_t s
     io.gamma64 = gamma;
     io.lam = gae_lambda;
     return launch_rollout(e, "rr_rollout_collect", true, params, precision, seed, iter, io, stream);
+}
+
+int rr_policy_evaluate(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
+                       const rr_eval_out* out, float* obs, void* stream)
+{
+    if (!e) return fail(RR_EINVAL, "rr_policy_evaluate: null handle");
+    if (!params || !out || !out->episodes)
+        return fail(RR_EINVAL, "rr_policy_evaluate: params, out and out->episodes must not be null");
+    if (((uintptr_t)params & 15) != 0) return fail(RR_EINVAL, "rr_policy_evaluate: params must be 16-B aligned");
+    if (precision != RR_POLICY_FP32 && precision != RR_POLICY_BF16 && precision != RR_POLICY_FP16X3)
+        return fail(RR_EINVAL,
+                    "rr_policy_evaluate: precision must be RR_POLICY_FP32, RR_POLICY_BF16 or RR_POLICY_FP16X3");
+    if (e->p.integrator == RR_INT_DOPRI5)
+        return fail(RR_EINVAL, "rr_policy_evaluate: RR_INT_DOPRI5 envs are evaluated step by step (rr_step)");
+    if (!(e->p.flags & RR_FLAG_AUTO_RESET))
+        return fail(RR_EINVAL, "rr_policy_evaluate: the handle needs RR_FLAG_AUTO_RESET (episodes follow one another)");
+    if (n_episodes < 1) return fail(RR_EINVAL, "rr_policy_evaluate: n_episodes must be at least 1");
+    if (max_steps <= 0) max_steps = (int64_t)n_episodes * e->p.max_episode_steps;
+    if (max_steps <= 0)
+        return fail(RR_EINVAL, "rr_policy_evaluate: an env without a TimeLimit needs max_steps > 0");
+    DeviceGuard g(e->device);
+    EvalIO io = {};
+    io.params = params;
+    io.episodes = out->episodes;
+    io.ep_return = out->ep_return;
+    io.ep_length = out->ep_length;
+    io.flags = out->flags;
+    io.used_mass = out->used_mass;
+    io.final_state = out->final_state;
+    io.obs = obs;
+    io.max_steps = (uint64_t)max_steps;
+    io.n_episodes = n_episodes;
+    io.obs_vec_ok = ((uintptr_t)obs & 15u) == 0;
+    const Bufs b = bufs_of(e);
+    const uint32_t mode = e->p.flags | kModeCounter;  // an auto-reset handle keeps counter words
+    const unsigned grid = (unsigned)((e->n + rol::kEnvsPerBlock - 1) / rol::kEnvsPerBlock);
+    const int prec = precision == RR_POLICY_BF16 ? 1 : precision == RR_POLICY_FP16X3 ? 2 : 0;
+    // compiled in the collect translation unit (rocket_collect.hip), as the collect kernel it derives from
+    const hipError_t err = (hipError_t)rrc_launch_eval(e->p.model, e->p.integrator, prec, grid, e->state, (uint32_t)e->n,
+                                                       mode, &e->kp, &b, &io, stream);
+    if (err != hipSuccess) return hip_fail(err, "rr_policy_evaluate: launch");
+    note_stream(e, stream);
+    return RR_OK;
 }
 
 int rr_gae(int64_t T, int64_t n, const float* rewards, const float* values, const float* starts,

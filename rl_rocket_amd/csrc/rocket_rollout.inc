@@ -229,10 +229,12 @@ __device__ __forceinline__ void regs_x(const float* o, typename pol::XOp<PREC>::
 // so their latency runs under that stage's transcendentals instead of stalling the head's FMA chain
 // at every read; the main TU's per-step kernels read them where used (the ~128 registers of early
 // head weights would cost them their second wave per SIMD).
+// VALUE = false (rr_policy_evaluate, rocket_eval.inc) runs the pi tower and the action heads only:
+// `value` is then 0 and the stages p = 1..4 are not stamped.
 struct NoStamp {
     __device__ __forceinline__ void operator()(int) const {}
 };
-template <int NS, int NA, int PREC, int NTW, class ST = NoStamp>
+template <int NS, int NA, int PREC, int NTW, bool VALUE = true, class ST = NoStamp>
 __device__ __forceinline__ void policy_forward(const float* sp,
                                                const typename pol::XOp<PREC>::T (&x)[NTW][pol::Layout<NS, NA, PREC>::KP1],
                                                uint32_t lane, float& value, float (&mean)[NA], ST stamp = ST())
@@ -242,11 +244,14 @@ __device__ __forceinline__ void policy_forward(const float* sp,
     const int half = lane >> 5;
     if constexpr (!kPolPrefetchA) {
         f32x16 h2[2][NTW];
-        pol::tower<NS, NA, PREC, NTW>(sp + L::VF, x, lane, h2);
-        stamp(1);
-        const float va = pol::head_dot<NTW>(sp + L::HV, h2, 0, half) + sp[L::VB];
-        const float vb = pol::head_dot<NTW>(sp + L::HV, h2, NTW - 1, half) + sp[L::VB];
-        value = (NTW == 2 && half) ? vb : va;
+        value = 0.0f;
+        if constexpr (VALUE) {
+            pol::tower<NS, NA, PREC, NTW>(sp + L::VF, x, lane, h2);
+            stamp(1);
+            const float va = pol::head_dot<NTW>(sp + L::HV, h2, 0, half) + sp[L::VB];
+            const float vb = pol::head_dot<NTW>(sp + L::HV, h2, NTW - 1, half) + sp[L::VB];
+            value = (NTW == 2 && half) ? vb : va;
+        }
         pol::tower<NS, NA, PREC, NTW>(sp + L::PI, x, lane, h2);
 #pragma unroll
         for (int a = 0; a < NA; ++a) {
@@ -257,19 +262,22 @@ __device__ __forceinline__ void policy_forward(const float* sp,
         return;
     }
     f32x16 h1[2][NTW], h2[2][NTW];
-    pol::tower_l1<NS, NA, PREC, NTW>(sp + L::VF, x, lane, h1);
-    stamp(1);
-    pol::tower_act1<PREC, NTW, FOLD>(h1);
-    stamp(2);
-    pol::tower_l2<NS, NA, PREC, NTW>(sp + L::VF, h1, lane, h2);
-    stamp(3);
-    const pol::HeadW wv = pol::load_head(sp + L::HV, half);
-    __builtin_amdgcn_sched_barrier(0);
-    pol::tower_act2<PREC, NTW, FOLD>(h2);
-    const float va = pol::head_dot_w<NTW>(wv, h2, 0) + sp[L::VB];
-    const float vb = pol::head_dot_w<NTW>(wv, h2, NTW - 1) + sp[L::VB];
-    value = (NTW == 2 && half) ? vb : va;
-    stamp(4);
+    value = 0.0f;
+    if constexpr (VALUE) {
+        pol::tower_l1<NS, NA, PREC, NTW>(sp + L::VF, x, lane, h1);
+        stamp(1);
+        pol::tower_act1<PREC, NTW, FOLD>(h1);
+        stamp(2);
+        pol::tower_l2<NS, NA, PREC, NTW>(sp + L::VF, h1, lane, h2);
+        stamp(3);
+        const pol::HeadW wv = pol::load_head(sp + L::HV, half);
+        __builtin_amdgcn_sched_barrier(0);
+        pol::tower_act2<PREC, NTW, FOLD>(h2);
+        const float va = pol::head_dot_w<NTW>(wv, h2, 0) + sp[L::VB];
+        const float vb = pol::head_dot_w<NTW>(wv, h2, NTW - 1) + sp[L::VB];
+        value = (NTW == 2 && half) ? vb : va;
+        stamp(4);
+    }
     pol::tower_l1<NS, NA, PREC, NTW>(sp + L::PI, x, lane, h1);
     stamp(5);
     pol::tower_act1<PREC, NTW, FOLD>(h1);
