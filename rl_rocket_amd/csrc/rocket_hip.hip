@@ -43,6 +43,16 @@
 
 namespace {
 
+// The workgroup barrier of the helper-wave kernels' entry. It orders LDS only (the flag clear before
+// the helpers' publish): unlike __syncthreads() it carries no fence over global memory, so the
+// loads issued before it stay in flight across it.
+__device__ __forceinline__ void entry_barrier()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
 // The step kernel: one env per lane, 64 envs per wave.
 // HELP (N <= kHelpMaxN, about one main wave per SIMD): the auto-reset candidates of main
 // wave k are drawn by helper wave WPB + k of the same workgroup (on the same SIMD) into
@@ -75,8 +85,6 @@ __global__ __launch_bounds__(HELP ? 2 * WPB * kWave : WPB * kWave) __attribute__
     const uint32_t n = n_envs;
     RR_STAMPS_BEGIN(4);  // diagnostic builds only (rocket_stamps.h)
     if constexpr (HELP) {
-        if (wv < (uint32_t)WPB && lane == 0) cflag[wv] = 0u;
-        __syncthreads();  // flags cleared before any helper can publish
         if (wv >= (uint32_t)WPB) {
             // the helper role reads its parameters through the device copy (B.kp): kernel-argument
             // values it used were loaded in the kernel's entry block and kept live into the main
@@ -85,7 +93,9 @@ __global__ __launch_bounds__(HELP ? 2 * WPB * kWave : WPB * kWave) __attribute__
             const uint32_t k = wv - WPB;  // the main wave this helper serves
             const uint32_t base = (blockIdx.x * WPB + k) * kWave;
             const uint32_t ih = min(base + lane, n - 1);
+            // the counter word is in flight across the barrier (see the main role below)
             const uint32_t cwh = (base < n && (mode & kModeCounter)) ? at(B.counter, ih) : 0u;
+            entry_barrier();
             if ((mode & RR_FLAG_AUTO_RESET) && base < n) {
                 float s_[NS], v_;
                 ResetStream key = reset_stream(P.seed_w, P.id_off + base + lane, cwh);
@@ -101,8 +111,10 @@ __global__ __launch_bounds__(HELP ? 2 * WPB * kWave : WPB * kWave) __attribute__
     }
     const uint32_t wave_idx = blockIdx.x * WPB + wv;
     const uint32_t wave_base = wave_idx * kWave;
-    if (wave_base >= n) return;  // wave-uniform
-    RR_STAMP(0);
+    if constexpr (!HELP) {
+        if (wave_base >= n) return;  // wave-uniform
+        RR_STAMP(0);
+    }
     const uint32_t i = wave_base + lane;
     const bool valid = i < n;
     const uint32_t ic = valid ? i : n - 1;
@@ -136,6 +148,17 @@ __global__ __launch_bounds__(HELP ? 2 * WPB * kWave : WPB * kWave) __attribute__
     // the SGPR -> VGPR copies of the pinned per-axis parameters issue here, in the shadow of
     // the state loads; left to the scheduler they landed after the load wait, inside the RK4
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (HELP) {
+        // HELP: the flag clear and the workgroup barrier (no helper may publish before the flag is
+        // cleared) come after every load of this wave has been issued: the barrier waits until all
+        // 2 * WPB waves of the workgroup have been dispatched, and that wait now passes inside the
+        // load round trip instead of in front of it. The early exit stays behind the barrier, so
+        // that every wave reaches it; an empty wave's loads above read env n - 1 (ic), in bounds.
+        if (lane == 0) cflag[wv] = 0u;
+        entry_barrier();
+        if (wave_base >= n) return;  // wave-uniform
+        RR_STAMP(0);
+    }
     // SB3 auto-reset candidate of this step, keyed on (gid, counter word): ~190 VALU right
     // after the counter word lands, instead of in the done branch of the waves that finish
     // last. Used by done lanes only. (HELP: drawn by the helper wave instead.)
@@ -200,10 +223,14 @@ __global__ __launch_bounds__(HELP ? 2 * WPB * kWave : WPB * kWave) __attribute__
     }
     cw = CL.with_elapsed(cw, el);
 
+    // HELP: the tail tests the mode word itself: `use_counter` kept from the entry as a lane mask
+    // was live across the whole kernel and spilled (2 SGPRs) once the entry barrier moved
+    uint32_t mode_t = mode;
+    if constexpr (HELP) pin_s(mode_t);
     if (valid) {
 #pragma unroll
         for (int j = 0; j < NS; ++j) bst_f<SA>(st_r, y1[j], vo, j * plane);
-        if (use_counter) bst_u<SA>(st_r, cw, vo, (NS + 1) * plane);
+        if (HELP ? (mode_t & kModeCounter) != 0u : use_counter) bst_u<SA>(st_r, cw, vo, (NS + 1) * plane);
         if (mode & RR_FLAG_EPISODE_STATS) bst_f<SA>(st_r, ret, vo, (NS + 2) * plane);
         store_outputs<NT, !ROWS>(io, i, vo, plane, n, r, done, trunc, t, bv, event ? 1.0f : (nf ? -1.0f : 0.0f));
     }

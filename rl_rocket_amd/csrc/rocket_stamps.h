@@ -8,6 +8,8 @@
 // entry to stamp 0, lane k those from stamp k - 1 to stamp k, and with rt the lanes N and N + 1 the
 // wave's s_memrealtime at entry / at the write (100 MHz, low 32 bits, as float bit patterns); the
 // values overwrite dst[i] (a per-env output such as the reward) of the wave's first lanes.
+// step_kernel's phase 0 reads "entry -> past the helper barrier, loads in flight": the helper-wave
+// kernels issue every load ahead of the barrier, so phase 1 (-> state landed) starts inside the round trip.
 // Accumulated stamps (the collect's step loop): RR_ACC_BEGIN(N), RR_ST(p) adds the cycles since
 // the previous stamp to phase p, RR_ACC_WRITE(dst, base, lane, ok) writes phase `lane` to dst[base + lane].
 #pragma once

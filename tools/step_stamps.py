@@ -4,7 +4,8 @@ the reward of the wave's first 6 envs; rocket_hip.hip step_kernel).
 
     RR_LIB_PATH=tools/ab/lib_sstamps.so python tools/step_stamps.py [--n 65536] --out F
 
-Phases per main wave: 0 kernel entry -> after the workgroup barrier (helper-wave kernels), 1 ->
+Phases per main wave: 0 kernel entry -> past the workgroup barrier with the loads in flight
+(helper-wave kernels issue every load ahead of the barrier; the plain kernels have none), 1 ->
 the state planes landed, 2 the step's compute (integration, event, reward, obs), 3 the tail (done
 compaction, terminal rows / reset, every output store issued). From the 100 MHz real-time clock:
 the spread of the waves' start times (dispatch ramp) and of their end times (the launch ends with
@@ -19,7 +20,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PHASES = ["entry->barrier", "->state landed", "compute", "tail (outputs issued)"]
+PHASES = ["entry->past the barrier, loads in flight", "->state landed", "compute", "tail (outputs issued)"]
 
 
 def main():
