@@ -43,6 +43,9 @@
 extern "C" {
 #endif
 
+/* 14: rr_policy_evaluate. rr_policy_evaluate_trace / rr_eval_trace joined ABI 14 later as a pure
+ * addition (no existing declaration changed), so the number did not move: a caller that needs the
+ * recording entry point looks the symbol up. */
 #define RR_ABI_VERSION 14
 
 /* error codes */
@@ -403,6 +406,42 @@ typedef struct rr_eval_out {      /* device pointers; planes are [n_episodes][n]
 
 int rr_policy_evaluate(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
                        const rr_eval_out* out, float* obs /* [n][state_dim] or NULL */, void* stream);
+
+/* ---- Recording evaluation: whole episodes of chosen envs (ABI 14, added without a version bump:
+ * a new symbol and a new struct, nothing existing changes) ----
+ * Replaces the per-episode histories the reference keeps while an EpisodeAnalyzer-wrapped env is
+ * evaluated (wrappers.py:189-235: info["rewards_dict"] of every step, ep_history/states, /actions,
+ * /vtarg, /rewards and the two 3D trajectory figures, all read from SIM.states / SIM.actions) and
+ * the reward terms of rocket_env.py:1016-1034 (rewards_dict), for the envs the caller chooses.
+ * rr_policy_evaluate_trace IS rr_policy_evaluate (same arithmetic in the same order, same reset
+ * draws, same rr_eval_out rows, same state left in the handle) and additionally, for every env i
+ * with slot[i] = s in [0, n_slots) and every step t = 0, 1, ... it takes in episode k < n_episodes:
+ *   state [s][k][t + 1][:]  the un-normalised state after the step, BEFORE any reset (SIM.states);
+ *                           row 0 is the state the episode starts from (k = 0: the state at the
+ *                           call; k > 0: the auto-reset draw)
+ *   action[s][k][t][:]      the clipped mean action the env stepped with
+ *   terms [s][k][t][:]      the step's reward terms (rr_buffers terms order) followed by its reward
+ *   length[k][s]            the steps episode k took in this call, written when it ends; an episode
+ *                           cut by max_steps gets its partial count when the launch ends
+ * t counts the steps of THIS call (not the TimeLimit's elapsed field: the handle may be
+ * mid-episode). Steps at t >= steps are not written but still counted in length, so length > steps
+ * marks a clipped record. Rows past an episode's length, rows of episodes never started and every
+ * row of a slot no env maps to are left untouched. slot values outside [0, n_slots) (-1 by
+ * convention) record nothing; two envs must not share a slot.
+ * RR_EINVAL: as rr_policy_evaluate, and trace, trace->slot, trace->state or trace->length NULL,
+ * n_slots < 1, steps < 1. Asynchronous, capturable, no allocation. */
+typedef struct rr_eval_trace {
+    const int32_t* slot;   /* device [n]: trace slot of env i in [0, n_slots), anything else = not recorded */
+    int32_t n_slots;       /* K >= 1 */
+    int32_t steps;         /* S >= 1: recorded steps per episode (capacity) */
+    float* state;          /* [n_slots][n_episodes][steps + 1][state_dim] */
+    float* action;         /* [n_slots][n_episodes][steps][action_dim] or NULL */
+    float* terms;          /* [n_slots][n_episodes][steps][n_terms + 1] or NULL */
+    int32_t* length;       /* [n_episodes][n_slots] */
+} rr_eval_trace;
+
+int rr_policy_evaluate_trace(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
+                             const rr_eval_out* out, const rr_eval_trace* trace, float* obs, void* stream);
 
 /* RolloutBuffer.compute_returns_and_advantage: rewards / values / starts [T][n] (starts[t]
  * = episode-start flag of step t), last_value / last_done [n] -> advantages, returns [T][n].

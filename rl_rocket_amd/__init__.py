@@ -10,13 +10,14 @@ with the reference's gym-0.21 surface on top:
   * ``Rocket6DOF`` / ``Rocket`` — single-env gym.Env shims with the reference's API,
     registered as ``my_environment/Falcon6DOF-v0`` / ``Falcon3DOF-v0`` when gym is present.
   * ``PolicyEvaluator`` / ``evaluate_policy`` / ``EvalResult`` — deterministic evaluation of a
-    policy over whole episodes on the device (``rl_rocket_amd.rollout``).
+    policy over whole episodes on the device (``rl_rocket_amd.rollout``); with ``record=`` it also
+    keeps whole episodes of chosen envs (``EvalTrace`` / ``EpisodeRecord``).
 """
 from .params import (ENV_CONFIG_6DOF, DEFAULTS_6DOF, DEFAULTS_3DOF, MAX_EPISODE_STEPS,  # noqa: F401
                      make_config, lower)
 
 __all__ = ["RocketBatch", "RocketVecEnv", "RocketVectorEnv", "Rocket6DOF", "Rocket", "ENV_CONFIG_6DOF",
-           "make_config", "PolicyEvaluator", "EvalResult", "evaluate_policy"]
+           "make_config", "PolicyEvaluator", "EvalResult", "evaluate_policy", "EvalTrace", "EpisodeRecord"]
 
 
 def __getattr__(name):
@@ -29,7 +30,7 @@ def __getattr__(name):
     if name in ("Rocket6DOF", "Rocket"):
         from . import envs
         return getattr(envs, name)
-    if name in ("PolicyEvaluator", "EvalResult", "evaluate_policy"):
+    if name in ("PolicyEvaluator", "EvalResult", "evaluate_policy", "EvalTrace", "EpisodeRecord"):
         from . import rollout
         return getattr(rollout, name)
     raise AttributeError(name)

@@ -94,6 +94,20 @@ class RrEvalOut(ctypes.Structure):
     ]
 
 
+class RrEvalTrace(ctypes.Structure):
+    """Mirror of ``rr_eval_trace`` (device pointers; ``action`` / ``terms`` may be NULL)."""
+
+    _fields_ = [
+        ("slot", ctypes.c_void_p),
+        ("n_slots", ctypes.c_int32),
+        ("steps", ctypes.c_int32),
+        ("state", ctypes.c_void_p),
+        ("action", ctypes.c_void_p),
+        ("terms", ctypes.c_void_p),
+        ("length", ctypes.c_void_p),
+    ]
+
+
 # symbol -> (restype, argtypes); the test suite checks this against include/rocket_hip.h
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -136,6 +150,8 @@ SIGNATURES = {
                                           ctypes.c_double] + [_P] * 17),
     "rr_policy_evaluate": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                           ctypes.POINTER(RrEvalOut), _P, _P]),
+    "rr_policy_evaluate_trace": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                ctypes.POINTER(RrEvalOut), ctypes.POINTER(RrEvalTrace), _P, _P]),
     "rr_gae": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P,
                               _P, _P]),
     "rr_clip_adam_workspace_size": (ctypes.c_int, [ctypes.c_int64, _P]),

@@ -21,6 +21,11 @@ EXACT_FLAGS = ["-mllvm", "-amdgpu-schedule-metric-bias=100"]
 # round 4; the learner's minibatch 3 % faster, round 6)
 SRC_COLLECT = os.path.join(HERE, "csrc", "rocket_collect.hip")
 COLLECT_FLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
+# the recording evaluation kernels (rr_policy_evaluate_trace), the collect TU's settings in a module
+# of their own: next to eval_kernel they changed its machine code (see the file's head). It sits in
+# a directory of its own: csrc/ itself holds the three translation units above and what they include
+# (tests/test_build_sources.py)
+SRC_EVAL_TRACE = os.path.join(HERE, "csrc", "eval_trace", "rocket_eval_trace.hip")
 HEADER = os.path.join(ROOT, "include", "rocket_hip.h")
 OUT = os.path.join(HERE, "librocket_hip.so")
 # benchmark-only helper (not part of the product ABI): bench.py's event-timed direct-launch region
@@ -56,11 +61,12 @@ def command(resource_usage=False, out=OUT, defines=(), extra=(), src=SRC, compil
 
 
 def sources():
-    """Every file the three translation units are compiled from: all of csrc/ and the C-ABI header,
-    sorted (tests/test_build_sources.py checks that the #include graph stays inside this list)."""
+    """Every file the translation units are compiled from: all of csrc/, the recording evaluation's
+    translation unit (which includes only files of csrc/) and the C-ABI header, sorted
+    (tests/test_build_sources.py checks that the #include graph stays inside this list)."""
     csrc = os.path.join(HERE, "csrc")
     return sorted([os.path.join(csrc, f) for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))]
-                  + [HEADER])
+                  + [SRC_EVAL_TRACE, HEADER])
 
 
 def source_hash():
@@ -79,20 +85,23 @@ def source_hash():
 
 
 def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
-    """The four steps of the library build: the main, exact-mode and collect translation units
-    compiled to objects (the latter two with EXACT_FLAGS / COLLECT_FLAGS), then linked into `out`."""
-    o_main, o_exact, o_coll = out + ".main.o", out + ".exact.o", out + ".collect.o"
+    """The five steps of the library build: the main, exact-mode, collect and recording-evaluation
+    translation units compiled to objects (the latter three with EXACT_FLAGS / COLLECT_FLAGS /
+    COLLECT_FLAGS), then linked into `out`."""
+    o_main, o_exact, o_coll, o_trace = out + ".main.o", out + ".exact.o", out + ".collect.o", out + ".evaltrace.o"
     c1 = command(resource_usage, o_main, defines, extra, SRC, compile_only=True, preload=preload)
     c2 = command(resource_usage, o_exact, defines, list(extra) + EXACT_FLAGS, SRC_EXACT, compile_only=True,
                  preload=preload)
     c3 = command(resource_usage, o_coll, defines, list(extra) + COLLECT_FLAGS, SRC_COLLECT, compile_only=True,
                  preload=preload)
-    c4 = [hipcc(), "--offload-arch=%s" % ARCH, "-shared", "-fPIC", "-o", out, o_main, o_exact, o_coll]
-    return [c1, c2, c3, c4]
+    c4 = command(resource_usage, o_trace, defines, list(extra) + COLLECT_FLAGS, SRC_EVAL_TRACE, compile_only=True,
+                 preload=preload)
+    c5 = [hipcc(), "--offload-arch=%s" % ARCH, "-shared", "-fPIC", "-o", out, o_main, o_exact, o_coll, o_trace]
+    return [c1, c2, c3, c4, c5]
 
 
 def build_lib(out=OUT, defines=(), extra=(), resource_usage=False, verbose=True, preload=4):
-    """Compile the three translation units (in parallel) and link `out`."""
+    """Compile the four translation units (in parallel) and link `out`."""
     cmds = commands(resource_usage, out, defines, extra, preload=preload)
     if verbose:
         for c in cmds:

@@ -1,5 +1,6 @@
-// rocket_device.h — the device code shared by the three translation units of librocket_hip.so
-// (rocket_hip.hip, rocket_exact.hip, rocket_collect.hip): the constants and the host-derived
+// rocket_device.h — the device code shared by the four translation units of librocket_hip.so
+// (rocket_hip.hip, rocket_exact.hip, rocket_collect.hip, eval_trace/rocket_eval_trace.hip): the
+// constants and the host-derived
 // parameter blocks (KParams, XParams), the buffer / intrinsic wrappers, the reset stream, the
 // RHS, integrators and ground event, reward and bounds, the obs tile store and the per-env
 // loads / stores that every step kernel inlines (physics_step, store_terminal, store_outputs).
@@ -1094,10 +1095,11 @@ static_assert(std::is_trivially_copyable_v<StepIO>, "StepIO crosses TUs by memcp
 }  // namespace
 
 // The hidden entry points (not part of the C-ABI) through which the main translation unit launches
-// the kernels compiled in the other two. Defined in rocket_exact.hip / rocket_collect.hip; the
+// the kernels compiled in the others. Defined in rocket_exact.hip / rocket_collect.hip /
+// eval_trace/rocket_eval_trace.hip (rrc_launch_eval_trace); the
 // main TU adds weak stand-ins, so that a library built from rocket_hip.hip alone still loads.
 // xp / kp / bufs / io / launch point to the caller's XParams / KParams / Bufs / StepIO, RolloutIO or
-// EvalIO / PpoLaunch.
+// EvalIO (trace: EvalTraceIO) / PpoLaunch.
 extern "C" {
 __attribute__((visibility("hidden"))) int rrx_launch_exact(int model, int variant, const void* xp, const void* bufs,
                                                            const void* io, double* state64, unsigned grid,
@@ -1108,5 +1110,9 @@ __attribute__((visibility("hidden"))) int rrc_launch_collect(int model, int inte
 __attribute__((visibility("hidden"))) int rrc_launch_eval(int model, int integ, int prec, unsigned grid, float* state,
                                                           uint32_t n, uint32_t mode, const void* kp,
                                                           const void* bufs, const void* io, void* stream);
+__attribute__((visibility("hidden"))) int rrc_launch_eval_trace(int model, int integ, int prec, unsigned grid,
+                                                                float* state, uint32_t n, uint32_t mode,
+                                                                const void* kp, const void* bufs, const void* io,
+                                                                const void* trace, void* stream);
 __attribute__((visibility("hidden"))) int rrc_launch_learner(const void* launch, void* stream);
 }

@@ -354,7 +354,7 @@ __global__ __launch_bounds__(kBlock) void narrow_kernel(const double* src, float
 
 // defined by the exact / collect translation units (declared in rocket_device.h); these weak
 // stand-ins (a library built from this file alone, e.g. a tools/ A/B variant) make RR_INT_DOPRI5
-// steps, rr_rollout_collect, rr_policy_evaluate and the learner fail loudly instead of failing to load
+// steps, rr_rollout_collect, rr_policy_evaluate(_trace) and the learner fail loudly instead of failing to load
 extern "C" __attribute__((weak, visibility("hidden"))) int rrx_launch_exact(int, int, const void*, const void*,
                                                                           const void*, double*, unsigned, void*)
 {
@@ -369,6 +369,13 @@ extern "C" __attribute__((weak, visibility("hidden"))) int rrc_launch_collect(in
 extern "C" __attribute__((weak, visibility("hidden"))) int rrc_launch_eval(int, int, int, unsigned, float*, uint32_t,
                                                                          uint32_t, const void*, const void*,
                                                                          const void*, void*)
+{
+    return (int)hipErrorInvalidDeviceFunction;
+}
+extern "C" __attribute__((weak, visibility("hidden"))) int rrc_launch_eval_trace(int, int, int, unsigned, float*,
+                                                                               uint32_t, uint32_t, const void*,
+                                                                               const void*, const void*, const void*,
+                                                                               void*)
 {
     return (int)hipErrorInvalidDeviceFunction;
 }
@@ -1476,24 +1483,35 @@ int rr_rollout_collect(rr_env* e, const float* params, int precision, uint64_t s
     return launch_rollout(e, "rr_rollout_collect", true, params, precision, seed, iter, io, stream);
 }
 
-int rr_policy_evaluate(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
-                       const rr_eval_out* out, float* obs, void* stream)
+namespace {
+
+// rr_policy_evaluate (trace == nullptr) and rr_policy_evaluate_trace: the argument checks, the
+// kernel's EvalIO and the launch. `who` prefixes every message.
+int evaluate(rr_env* e, const char* who, const float* params, int precision, int n_episodes, int64_t max_steps,
+             const rr_eval_out* out, bool traced, const rr_eval_trace* trace, float* obs, void* stream)
 {
-    if (!e) return fail(RR_EINVAL, "rr_policy_evaluate: null handle");
+    const std::string w = std::string(who) + ": ";
+    if (!e) return fail(RR_EINVAL, w + "null handle");
     if (!params || !out || !out->episodes)
-        return fail(RR_EINVAL, "rr_policy_evaluate: params, out and out->episodes must not be null");
-    if (((uintptr_t)params & 15) != 0) return fail(RR_EINVAL, "rr_policy_evaluate: params must be 16-B aligned");
+        return fail(RR_EINVAL, w + "params, out and out->episodes must not be null");
+    if (((uintptr_t)params & 15) != 0) return fail(RR_EINVAL, w + "params must be 16-B aligned");
     if (precision != RR_POLICY_FP32 && precision != RR_POLICY_BF16 && precision != RR_POLICY_FP16X3)
-        return fail(RR_EINVAL,
-                    "rr_policy_evaluate: precision must be RR_POLICY_FP32, RR_POLICY_BF16 or RR_POLICY_FP16X3");
+        return fail(RR_EINVAL, w + "precision must be RR_POLICY_FP32, RR_POLICY_BF16 or RR_POLICY_FP16X3");
+    // the trace's own checks come before anything reads the handle
+    if (traced) {
+        if (!trace) return fail(RR_EINVAL, w + "trace must not be null");
+        if (!trace->slot || !trace->state || !trace->length)
+            return fail(RR_EINVAL, w + "trace->slot, trace->state and trace->length must not be null");
+        if (trace->n_slots < 1 || trace->steps < 1)
+            return fail(RR_EINVAL, w + "trace->n_slots and trace->steps must be at least 1");
+    }
     if (e->p.integrator == RR_INT_DOPRI5)
-        return fail(RR_EINVAL, "rr_policy_evaluate: RR_INT_DOPRI5 envs are evaluated step by step (rr_step)");
+        return fail(RR_EINVAL, w + "RR_INT_DOPRI5 envs are evaluated step by step (rr_step)");
     if (!(e->p.flags & RR_FLAG_AUTO_RESET))
-        return fail(RR_EINVAL, "rr_policy_evaluate: the handle needs RR_FLAG_AUTO_RESET (episodes follow one another)");
-    if (n_episodes < 1) return fail(RR_EINVAL, "rr_policy_evaluate: n_episodes must be at least 1");
+        return fail(RR_EINVAL, w + "the handle needs RR_FLAG_AUTO_RESET (episodes follow one another)");
+    if (n_episodes < 1) return fail(RR_EINVAL, w + "n_episodes must be at least 1");
     if (max_steps <= 0) max_steps = (int64_t)n_episodes * e->p.max_episode_steps;
-    if (max_steps <= 0)
-        return fail(RR_EINVAL, "rr_policy_evaluate: an env without a TimeLimit needs max_steps > 0");
+    if (max_steps <= 0) return fail(RR_EINVAL, w + "an env without a TimeLimit needs max_steps > 0");
     DeviceGuard g(e->device);
     EvalIO io = {};
     io.params = params;
@@ -1511,12 +1529,41 @@ int rr_policy_evaluate(rr_env* e, const float* params, int precision, int n_epis
     const uint32_t mode = e->p.flags | kModeCounter;  // an auto-reset handle keeps counter words
     const unsigned grid = (unsigned)((e->n + rol::kEnvsPerBlock - 1) / rol::kEnvsPerBlock);
     const int prec = precision == RR_POLICY_BF16 ? 1 : precision == RR_POLICY_FP16X3 ? 2 : 0;
-    // compiled in the collect translation unit (rocket_collect.hip), as the collect kernel it derives from
-    const hipError_t err = (hipError_t)rrc_launch_eval(e->p.model, e->p.integrator, prec, grid, e->state, (uint32_t)e->n,
-                                                       mode, &e->kp, &b, &io, stream);
-    if (err != hipSuccess) return hip_fail(err, "rr_policy_evaluate: launch");
+    // compiled in the collect translation unit (rocket_collect.hip), as the collect kernel they derive from
+    hipError_t err;
+    if (traced) {
+        EvalTraceIO t = {};
+        t.slot = trace->slot;
+        t.state = trace->state;
+        t.action = trace->action;
+        t.terms = trace->terms;
+        t.length = trace->length;
+        t.n_slots = trace->n_slots;
+        t.steps = trace->steps;
+        err = (hipError_t)rrc_launch_eval_trace(e->p.model, e->p.integrator, prec, grid, e->state, (uint32_t)e->n, mode,
+                                                &e->kp, &b, &io, &t, stream);
+    } else {
+        err = (hipError_t)rrc_launch_eval(e->p.model, e->p.integrator, prec, grid, e->state, (uint32_t)e->n, mode,
+                                          &e->kp, &b, &io, stream);
+    }
+    if (err != hipSuccess) return hip_fail(err, (w + "launch").c_str());
     note_stream(e, stream);
     return RR_OK;
+}
+
+}  // namespace
+
+int rr_policy_evaluate(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
+                       const rr_eval_out* out, float* obs, void* stream)
+{
+    return evaluate(e, "rr_policy_evaluate", params, precision, n_episodes, max_steps, out, false, nullptr, obs, stream);
+}
+
+int rr_policy_evaluate_trace(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
+                             const rr_eval_out* out, const rr_eval_trace* trace, float* obs, void* stream)
+{
+    return evaluate(e, "rr_policy_evaluate_trace", params, precision, n_episodes, max_steps, out, true, trace, obs,
+                    stream);
 }
 
 int rr_gae(int64_t T, int64_t n, const float* rewards, const float* values, const float* starts,

@@ -24,6 +24,85 @@ from .params import (ACTION_NAMES_3DOF, ACTION_NAMES_6DOF, MAX_GIMBAL, MAX_THRUS
                      STATE_NAMES_6DOF, config_3dof, config_6dof)
 
 
+# ---- one episode's derived views, shared by the shims below and by the recorded episodes of the
+# ---- one-launch evaluation (eval_trace.EpisodeRecord) ----
+
+def denormalize_action(model, action, max_gimbal=MAX_GIMBAL, max_thrust=MAX_THRUST):
+    """rocket_env.py:969-981 (6DOF) / :395-406 (3DOF), no clipping, float32."""
+    if model == 6:
+        return np.float32([action[0] * max_gimbal, action[1] * max_gimbal, (action[2] + 1) / 2.0 * max_thrust])
+    return np.float32([action[0] * max_gimbal, (action[1] + 1) / 2.0 * max_thrust])
+
+
+def compute_vtarg_6dof(state32, v_0, waypoint):
+    """rocket_env.py:986-1014: v_targ of one float32 state; v_0 = |v| of the episode's first state."""
+    r, v = state32[0:3].astype(np.float64), state32[3:6].astype(np.float64)
+    if r[0] > waypoint:
+        r_hat = r - [waypoint, 0, 0]
+        v_hat = v - [-2, 0, 0]
+        tau = 20
+    else:
+        r_hat = np.array([r[0] + 1, 0, 0])
+        v_hat = v - [-1, 0, 0]
+        tau = 100
+    t_go = np.linalg.norm(r_hat) / np.linalg.norm(v_hat)
+    return -v_0 * (r_hat / max(1e-3, np.linalg.norm(r_hat))) * (1 - np.exp(-t_go / tau))
+
+
+def compute_vtarg_3dof(state32, v_0, waypoint):
+    """rocket_env.py:219-247 (z is the altitude, no +1)."""
+    r, v = state32[0:2], state32[3:5]
+    if r[1] > waypoint:
+        r_hat = r - [0, waypoint]
+        v_hat = v - [0, -2]
+        tau = 20
+    else:
+        r_hat = [0, r[1]]
+        v_hat = v - [0, -1]
+        tau = 100
+    t_go = np.linalg.norm(r_hat) / np.linalg.norm(v_hat)
+    return -v_0 * (np.array(r_hat) / max(1e-3, np.linalg.norm(r_hat))) * (1 - np.exp(-t_go / tau))
+
+
+def plotly_go():
+    try:
+        import plotly.graph_objects as go
+    except ImportError as e:  # pragma: no cover - plotly ships with this image
+        raise ImportError("the episode figures (get_trajectory_plotly & co.) need plotly") from e
+    return go
+
+
+def path_figure(df, arrows, target_r=None, landing_target=None):
+    """A 6DOF episode's 3D path (x altitude, y, z) from its state dataframe `df`, `arrows` = (u, v, w)
+    columns drawn as cones along it, optionally the landing pad (a disc of radius target_r in the
+    x = 0 plane) and the landing target (rocket_env.py:861-950)."""
+    go = plotly_go()
+    u, v, w = (np.asarray(c, dtype=np.float64) for c in arrows)
+    k = min(len(df), len(u))  # vtarg rows: one per step; state rows: one more (the IC)
+    x, y, z = (df[c].to_numpy(dtype=np.float64) for c in ("x", "y", "z"))
+    traces = [go.Scatter3d(x=x, y=y, z=z, mode="lines", name="trajectory"),
+              go.Cone(x=x[:k], y=y[:k], z=z[:k], u=u[:k], v=v[:k], w=w[:k], sizeref=3, showscale=False)]
+    if target_r is not None:
+        r = float(target_r)
+        ax = np.linspace(-r, r, 100)
+        zz, yy = np.meshgrid(ax, ax)
+        disc = (zz * zz + yy * yy < r * r).astype(np.float64)
+        traces.append(go.Surface(x=disc, y=yy, z=zz, surfacecolor=disc, showscale=False, name="landing pad"))
+    fig = go.Figure(data=traces)
+    if landing_target is not None:
+        tx, ty, tz = (float(c) for c in landing_target)
+        fig.add_trace(go.Scatter3d(x=[tx], y=[ty], z=[tz], mode="markers", name="target"))
+        fig.update_layout(scene_camera={"up": {"x": 1, "y": 0, "z": 0}, "center": {"x": 0, "y": 0, "z": 0},
+                                        "eye": {"x": 0.625, "y": 1.25, "z": 0.0}})
+    fig.update_layout(scene_aspectmode="data")
+    return fig
+
+
+def attitude_figure(df):
+    go = plotly_go()
+    return go.Figure(data=[go.Scatter(x=df.index, y=df[c], mode="lines", name=c) for c in ("q0", "q1", "q2", "q3")])
+
+
 class _SimView:
     """The public surface of ``Simulator6DOF`` / ``Simulator3DOF`` that callers read
     (``states``, ``actions``, ``times``, ``state``, ``t``, ``timestep``; simulator.py:12-86, 179-257)."""
@@ -194,10 +273,7 @@ class Rocket6DOF(_RocketBase):
 
     def _denormalize_action(self, action):
         """rocket_env.py:969-981 (no clipping)"""
-        gimbal_y = action[0] * self.max_gimbal
-        gimbal_z = action[1] * self.max_gimbal
-        thrust = (action[2] + 1) / 2.0 * self.max_thrust
-        return np.float32([gimbal_y, gimbal_z, thrust])
+        return denormalize_action(6, action, self.max_gimbal, self.max_thrust)
 
     def _normalize_obs(self, obs):
         return (obs / self.state_normalizer).astype("float32")
@@ -207,18 +283,8 @@ class Rocket6DOF(_RocketBase):
 
     def _compute_vtarg(self, state32):
         """rocket_env.py:986-1014 (host side, for vtarg_history only)."""
-        r, v = state32[0:3].astype(np.float64), state32[3:6].astype(np.float64)
         v_0 = np.linalg.norm(np.asarray(self.SIM.states[0][3:6], dtype=np.float32))
-        if r[0] > self.waypoint:
-            r_hat = r - [self.waypoint, 0, 0]
-            v_hat = v - [-2, 0, 0]
-            tau = 20
-        else:
-            r_hat = np.array([r[0] + 1, 0, 0])
-            v_hat = v - [-1, 0, 0]
-            tau = 100
-        t_go = np.linalg.norm(r_hat) / np.linalg.norm(v_hat)
-        return -v_0 * (r_hat / max(1e-3, np.linalg.norm(r_hat))) * (1 - np.exp(-t_go / tau))
+        return compute_vtarg_6dof(state32, v_0, self.waypoint)
 
     def vtarg_to_dataframe(self):
         import pandas as pd
@@ -229,38 +295,12 @@ class Rocket6DOF(_RocketBase):
     # The reference's three figures (3D path with velocity cones over the landing pad, 3D path with the
     # target-velocity field and the landing target, the quaternion's components over time), built here by
     # one helper on plotly.graph_objects (imported lazily: plotting is off the step path).
-    @staticmethod
-    def _go():
-        try:
-            import plotly.graph_objects as go
-        except ImportError as e:  # pragma: no cover - plotly ships with this image
-            raise ImportError("the episode figures (get_trajectory_plotly & co.) need plotly") from e
-        return go
+    _go = staticmethod(plotly_go)
 
     def _path_figure(self, arrows, pad=False, target=False):
-        """The episode's 3D path (x altitude, y, z), `arrows` = (u, v, w) columns drawn as cones along
-        it, optionally the landing pad (a disc of radius target_r in the x = 0 plane) and the target."""
-        go = self._go()
-        df = self.states_to_dataframe()
-        u, v, w = (np.asarray(c, dtype=np.float64) for c in arrows)
-        k = min(len(df), len(u))  # vtarg rows: one per step; state rows: one more (the IC)
-        x, y, z = (df[c].to_numpy(dtype=np.float64) for c in ("x", "y", "z"))
-        traces = [go.Scatter3d(x=x, y=y, z=z, mode="lines", name="trajectory"),
-                  go.Cone(x=x[:k], y=y[:k], z=z[:k], u=u[:k], v=v[:k], w=w[:k], sizeref=3, showscale=False)]
-        if pad:
-            r = float(self.target_r)
-            ax = np.linspace(-r, r, 100)
-            zz, yy = np.meshgrid(ax, ax)
-            disc = (zz * zz + yy * yy < r * r).astype(np.float64)
-            traces.append(go.Surface(x=disc, y=yy, z=zz, surfacecolor=disc, showscale=False, name="landing pad"))
-        fig = go.Figure(data=traces)
-        if target:
-            tx, ty, tz = (float(c) for c in self.landing_target)
-            fig.add_trace(go.Scatter3d(x=[tx], y=[ty], z=[tz], mode="markers", name="target"))
-            fig.update_layout(scene_camera={"up": {"x": 1, "y": 0, "z": 0}, "center": {"x": 0, "y": 0, "z": 0},
-                                            "eye": {"x": 0.625, "y": 1.25, "z": 0.0}})
-        fig.update_layout(scene_aspectmode="data")
-        return fig
+        """path_figure of this env's episode so far."""
+        return path_figure(self.states_to_dataframe(), arrows, target_r=self.target_r if pad else None,
+                           landing_target=self.landing_target if target else None)
 
     def get_trajectory_plotly(self):
         df = self.states_to_dataframe()
@@ -271,9 +311,7 @@ class Rocket6DOF(_RocketBase):
         return self._path_figure((vt["v_x"], vt["v_y"], vt["v_z"]), target=True)
 
     def get_attitude_trajectory(self):
-        go = self._go()
-        df = self.states_to_dataframe()
-        return go.Figure(data=[go.Scatter(x=df.index, y=df[c], mode="lines", name=c) for c in ("q0", "q1", "q2", "q3")])
+        return attitude_figure(self.states_to_dataframe())
 
     @property
     def rotation_obj(self):
@@ -337,18 +375,7 @@ class Rocket(_RocketBase):
 
     def _compute_vtarg(self, state32):
         """rocket_env.py:219-247 (host side, for vtarg_history only; z is the altitude, no +1)."""
-        r, v = state32[0:2], state32[3:5]
-        v_0 = np.linalg.norm(self.SIM.states[0][3:5])
-        if r[1] > self.waypoint:
-            r_hat = r - [0, self.waypoint]
-            v_hat = v - [0, -2]
-            tau = 20
-        else:
-            r_hat = [0, r[1]]
-            v_hat = v - [0, -1]
-            tau = 100
-        t_go = np.linalg.norm(r_hat) / np.linalg.norm(v_hat)
-        return -v_0 * (np.array(r_hat) / max(1e-3, np.linalg.norm(r_hat))) * (1 - np.exp(-t_go / tau))
+        return compute_vtarg_3dof(state32, np.linalg.norm(self.SIM.states[0][3:5]), self.waypoint)
 
     def vtarg_to_dataframe(self):
         import pandas as pd
@@ -357,9 +384,7 @@ class Rocket(_RocketBase):
 
     def _denormalize_action(self, action):
         """rocket_env.py:395-406 (no clipping)"""
-        gimbal = action[0] * self.max_gimbal
-        thrust = (action[1] + 1) / 2.0 * self.max_thrust
-        return np.float32([gimbal, thrust])
+        return denormalize_action(3, action, self.max_gimbal, self.max_thrust)
 
     def _normalize_obs(self, obs):
         return obs / self.state_normalizer

@@ -990,6 +990,7 @@ class GraphedPPOUpdate:
 
 from ._lib import (RR_EVAL_BOUNDS as EVAL_BOUNDS, RR_EVAL_EVENT as EVAL_EVENT, RR_EVAL_LANDED as EVAL_LANDED,  # noqa: E402
                    RR_EVAL_NONFINITE as EVAL_NONFINITE, RR_EVAL_TRUNCATED as EVAL_TRUNCATED)
+from .eval_trace import EpisodeRecord, EvalTrace  # noqa: E402,F401
 
 
 class EvalResult:
@@ -997,11 +998,13 @@ class EvalResult:
     its buffers: the next ``run()`` overwrites them): ``episodes`` [n] (episodes env i completed),
     ``ep_return`` / ``ep_length`` / ``flags`` / ``used_mass`` [n_episodes, n] and ``final_state``
     [n_episodes, state_dim, n] (the terminal state, un-normalised). Row [k, i] is valid where
-    ``k < episodes[i]``; ``finished()`` is that mask."""
+    ``k < episodes[i]``; ``finished()`` is that mask. ``trace`` is the ``EvalTrace`` of the envs the
+    evaluator records (``PolicyEvaluator(record=...)``), else None."""
 
-    def __init__(self, episodes, ep_return, ep_length, flags, used_mass, final_state, state_names):
+    def __init__(self, episodes, ep_return, ep_length, flags, used_mass, final_state, state_names, trace=None):
         self.episodes, self.ep_return, self.ep_length, self.flags = episodes, ep_return, ep_length, flags
         self.used_mass, self.final_state, self.state_names = used_mass, final_state, list(state_names)
+        self.trace = trace
 
     def finished(self):
         k = torch.arange(self.ep_return.shape[0], device=self.episodes.device)
@@ -1054,9 +1057,22 @@ class PolicyEvaluator:
     state and the reward terms of each step come from a shadow batch without auto-reset stepped
     from the same state, and envs that have finished are put back after every step.
     ``max_steps`` (default ``n_episodes * max_episode_steps``) caps the steps of each env; episodes
-    not completed by then leave their rows untouched (``EvalResult.episodes`` counts)."""
+    not completed by then leave their rows untouched (``EvalResult.episodes`` counts).
 
-    def __init__(self, batch, policy, n_episodes=5, max_steps=None, policy_dtype="fp32", fused=None):
+    ``record`` (a sequence or tensor of env indices local to the batch, unique, any order) records
+    whole episodes of those envs: ``EvalResult.trace`` is then an ``EvalTrace`` with, per recorded
+    env and episode, the un-normalised state before the episode's first step and after every step,
+    the clipped mean actions, the reward terms and rewards, and the episode's length; its
+    ``episode(env_id, k)`` gives the dataframes and figures of the reference's ``EpisodeAnalyzer``.
+    The fused path does it in the same single launch (``rr_policy_evaluate_trace``); the evaluation
+    itself is bit for bit the unrecorded one. ``record_steps`` is the recorded steps per episode
+    (default ``max_episode_steps``; required without a TimeLimit): longer episodes are clipped, their
+    ``length`` still counts every step. An episode's step count starts at the call, and the v_targ
+    history takes v_0 from the first recorded state: reset first, as for whole episodes.
+    ``record=None`` is the plain evaluation (``rr_policy_evaluate``)."""
+
+    def __init__(self, batch, policy, n_episodes=5, max_steps=None, policy_dtype="fp32", fused=None, record=None,
+                 record_steps=None):
         from . import _lib
         from .params import STATE_NAMES_3DOF, STATE_NAMES_6DOF
 
@@ -1090,13 +1106,20 @@ class PolicyEvaluator:
         self.flags = torch.zeros((ne, n), dtype=torch.uint8, device=dev)
         self.used_mass = torch.zeros((ne, n), dtype=torch.float32, device=dev)
         self.final_state = torch.zeros((ne, ns, n), dtype=torch.float32, device=dev)
+        self.trace = self._make_trace(record, record_steps)
         self.result = EvalResult(self.episodes, self.ep_return, self.ep_length, self.flags, self.used_mass,
-                                 self.final_state, STATE_NAMES_6DOF if batch.model == 6 else STATE_NAMES_3DOF)
+                                 self.final_state, STATE_NAMES_6DOF if batch.model == 6 else STATE_NAMES_3DOF,
+                                 trace=self.trace)
         self._lib = _lib.load()
         if self.fused:
             self._pack = PolicyPack(policy, ns, na, dev, precision=policy_dtype)
             self._out = _lib.RrEvalOut(*[t.data_ptr() for t in (self.episodes, self.ep_return, self.ep_length,
                                                                  self.flags, self.used_mass, self.final_state)])
+            if self.trace is not None:
+                tr = self.trace
+                self._trace_io = _lib.RrEvalTrace(self._slot.data_ptr(), tr.state.shape[0], tr.steps,
+                                                  tr.state.data_ptr(), tr.action.data_ptr(), tr.terms.data_ptr(),
+                                                  tr.length.data_ptr())
             return
         from .batch import RocketBatch
         from .params import INTEGRATORS
@@ -1114,6 +1137,35 @@ class PolicyEvaluator:
         self._none = torch.zeros((n,), dtype=torch.uint8, device=dev)
         self._tlen = torch.zeros((n,), dtype=torch.int32, device=dev)
 
+    def _make_trace(self, record, record_steps):
+        """The slot plane ([n] int32: the trace slot of env i, -1 = not recorded) and the trace
+        buffers of ``record``, allocated once; None without ``record``."""
+        if record is None:
+            if record_steps is not None:
+                raise ValueError("record_steps needs record")
+            return None
+        env = self.env
+        n, dev = env.num_envs, env.device
+        ids = torch.as_tensor(record).reshape(-1).to(torch.int64).cpu()
+        if ids.numel() < 1:
+            raise ValueError("record must name at least one env")
+        if int(ids.min()) < 0 or int(ids.max()) >= n:
+            raise ValueError("record holds an env index outside [0, %d)" % n)
+        if ids.unique().numel() != ids.numel():
+            raise ValueError("record holds an env index twice")
+        steps = int(record_steps) if record_steps else int(env.params.max_episode_steps)
+        if steps < 1:
+            raise ValueError("an env without a TimeLimit needs record_steps")
+        k, ne = ids.numel(), self.n_episodes
+        slot = torch.full((n,), -1, dtype=torch.int32)
+        slot[ids] = torch.arange(k, dtype=torch.int32)
+        self._slot = slot.to(dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        return EvalTrace(env.cfg, torch.zeros((k, ne, steps + 1, env.state_dim), **f32),
+                         torch.zeros((k, ne, steps, env.action_dim), **f32),
+                         torch.zeros((k, ne, steps, env.n_terms + 1), **f32),
+                         torch.zeros((ne, k), dtype=torch.int32, device=dev), ids.to(dev), episodes=self.episodes)
+
     @torch.no_grad()
     def run(self):
         if not self.fused:
@@ -1125,6 +1177,12 @@ class PolicyEvaluator:
 
         env = self.env
         stream = ctypes.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
+        if self.trace is not None:
+            _lib.check(self._lib.rr_policy_evaluate_trace(env._h, _ptr(self._pack.pack()), self._pack.prec,
+                                                          self.n_episodes, self.max_steps, ctypes.byref(self._out),
+                                                          ctypes.byref(self._trace_io), _ptr(env.obs), stream),
+                       "rr_policy_evaluate_trace")
+            return self.result
         _lib.check(self._lib.rr_policy_evaluate(env._h, _ptr(self._pack.pack()), self._pack.prec, self.n_episodes,
                                                 self.max_steps, ctypes.byref(self._out), _ptr(env.obs), stream),
                    "rr_policy_evaluate")
@@ -1173,6 +1231,12 @@ class PolicyEvaluator:
         obs = env.reset(mask=self._none)  # no env is reset: the obs of the current state
         pre = self._snap(env)
         ep = torch.zeros_like(self.episodes)
+        tr = self.trace
+        if tr is not None:  # the kernel's records of the recorded envs, same rows, same tensors
+            ids, cap = tr.env_ids, tr.steps
+            ks = torch.arange(ids.numel(), device=ids.device)
+            t_rec = torch.zeros_like(ids)  # steps of the running episode taken in this call
+            tr.state[ks, 0, 0] = pre[0].float()[:, ids].T
         ret = pre[3].clone() if self._stats else torch.zeros_like(pre[3])
         m0 = pre[0][-1].float()
         for _ in range(self.max_steps):
@@ -1195,6 +1259,18 @@ class PolicyEvaluator:
             put_row(self.flags, ep, end, fl)
             put_row(self.used_mass, ep, end, m0 - y1[-1])
             put_row(self.final_state, ep, end, y1)
+            if tr is not None:
+                act_r, end_r, ep_r = active[ids], end[ids], ep[ids].long()
+                w = act_r & (t_rec < cap)  # steps past the capacity are counted, not written
+                kw, ew, tw = ks[w], ep_r[w], t_rec[w]
+                tr.state[kw, ew, tw + 1] = y1[:, ids].T[w]
+                tr.action[kw, ew, tw] = act[ids][w]
+                tr.terms[kw, ew, tw] = torch.cat([terms[:nt, ids].T, rew[ids, None]], dim=1)[w]
+                t_rec = t_rec + act_r.to(t_rec.dtype)
+                tr.length[ep_r[end_r], ks[end_r]] = t_rec[end_r].to(torch.int32)
+                t_rec = torch.where(end_r, torch.zeros_like(t_rec), t_rec)
+                nxt = end_r & (ep_r + 1 < ne)  # row 0 of the next episode: the auto-reset state
+                tr.state[ks[nxt], ep_r[nxt] + 1, 0] = post[0].float()[:, ids].T[nxt]
             ret = torch.where(end, torch.zeros_like(ret), ret)
             m0 = torch.where(end, post[0][-1].float(), m0)
             ep = ep + end.to(ep.dtype)
@@ -1202,6 +1278,9 @@ class PolicyEvaluator:
             pre = tuple(torch.where(active, b, a) for a, b in zip(pre, post))
             self._put(env, *pre)
         self.episodes.copy_(ep)
+        if tr is not None:  # episodes cut by max_steps: the steps they took so far
+            cut = ep[ids] < ne
+            tr.length[ep[ids].long()[cut], ks[cut]] = t_rec[cut].to(torch.int32)
         env.reset(mask=self._none)  # env.obs of the final state
         return self.result
 
