@@ -1,19 +1,18 @@
 // rocket_collect.hip — the third translation unit of librocket_hip.so: the rollout collect kernels
-// (rollout_step_kernel<..., MULTI = true>, rocket_rollout.inc: rr_rollout_collect), the evaluation
-// kernels (eval_kernel, rocket_eval.inc: rr_policy_evaluate, the collect's loop without its value
-// tower, launched through rrc_launch_eval) and the PPO
-// learner's kernels (rocket_ppo.inc: rr_ppo_grad / rr_ppo_update / rr_clip_adam, launched through
-// rrc_launch_learner), compiled with their own code-generation setting (rl_rocket_amd/build.py
-// COLLECT_FLAGS: -amdgpu-mfma-vgpr-form, the MFMA accumulators in VGPRs) without touching the other
-// kernels. In the AGPR form every tanh input of the policy towers first crosses back with a
-// v_accvgpr_read (384 in the collect loop); in the VGPR form the loop issues 12 % fewer VALU
-// instructions and the collect measured 5.5 % faster (profiles/r04/ab_vf/). The gradient kernel
+// (rollout_step_kernel<..., MULTI = true>, rocket_rollout.inc: rr_rollout_collect, launched through
+// rrc_launch_collect), the evaluation kernels (eval_kernel, rocket_eval.inc: rr_policy_evaluate, the
+// collect's loop without its value tower, launched through rrc_launch_eval) and the PPO learner's
+// kernels (rocket_ppo.inc: rr_ppo_grad / rr_ppo_update / rr_clip_adam, launched through
+// rrc_launch_learner). Each entry point takes the caller's launch record (rocket_device.h:
+// EnvLaunch, PpoLaunch) as bytes; the env kernels' instantiation is picked by dispatch_env_prec.
+// They are compiled with their own code-generation setting (rl_rocket_amd/build.py COLLECT_FLAGS:
+// -amdgpu-mfma-vgpr-form, the MFMA accumulators in VGPRs) without touching the other kernels. In the
+// AGPR form every tanh input of the policy towers first crosses back with a v_accvgpr_read (384 in
+// the collect loop); in the VGPR form the loop issues 12 % fewer VALU instructions and the collect
+// measured 5.5 % faster (profiles/r04/ab_vf/). The gradient kernel
 // moves 1 082 -> 343 registers between the files and its minibatch measured 3 % faster, bitwise
 // (profiles/r06/ppo_vf/). The same flag on the whole main TU would cost the per-step fp16x3
 // rollout kernels their second wave per SIMD.
-#include <cstring>
-#include <type_traits>
-
 #include "rocket_device.h"
 // layer-2 A fragments read a group ahead in this translation unit (see rocket_policy.inc)
 #define RR_POL_PREFETCH_A 1
@@ -76,64 +75,34 @@ __global__ __launch_bounds__(kAdamThreads) void adam_step_kernel(AdamList A, con
 }  // namespace
 
 // the collect's entry point (declared in rocket_device.h): one rr_rollout_collect launch,
-// rollout_step_kernel<MODEL, INTEG, PREC, MULTI = true, 2>. kp / bufs / io point to the KParams /
-// Bufs / RolloutIO of the calling TU.
-extern "C" int rrc_launch_collect(int model, int integ, int prec, unsigned grid, float* state, uint32_t n,
-                                  uint32_t mode, const void* kp, const void* bufs, const void* io, void* stream)
+// rollout_step_kernel<MODEL, INTEG, PREC, MULTI = true, 2>. launch / io point to the EnvLaunch /
+// RolloutIO of the calling TU.
+extern "C" int rrc_launch_collect(const void* launch, const void* io)
 {
-    KParams p;
-    Bufs b;
-    RolloutIO o;
-    std::memcpy(&p, kp, sizeof(KParams));
-    std::memcpy(&b, bufs, sizeof(Bufs));
-    std::memcpy(&o, io, sizeof(RolloutIO));
-    hipStream_t s = (hipStream_t)stream;
-#define RR_COLLECT(M, I, PR)                                                                                  \
-    hipLaunchKernelGGL((rollout_step_kernel<M, I, PR, true, 2>), dim3(grid), dim3(rol::Shape<2>::kThreads), 0, \
-                       s, state, n, mode, p, b, o)
-#define RR_COLLECT_P(M, I)                      \
-    do {                                        \
-        if (prec == 1) RR_COLLECT(M, I, 1);     \
-        else if (prec == 2) RR_COLLECT(M, I, 2); \
-        else RR_COLLECT(M, I, 0);               \
-    } while (0)
-    const bool euler = integ == RR_INT_EULER;
-    if (model == RR_MODEL_6DOF && !euler) RR_COLLECT_P(6, RR_INT_RK4);
-    else if (model == RR_MODEL_6DOF) RR_COLLECT_P(6, RR_INT_EULER);
-    else if (!euler) RR_COLLECT_P(3, RR_INT_RK4);
-    else RR_COLLECT_P(3, RR_INT_EULER);
-#undef RR_COLLECT_P
-#undef RR_COLLECT
+    const auto L = from_unit<EnvLaunch>(launch);
+    const auto p = from_unit<KParams>(L.kp);
+    const auto b = from_unit<Bufs>(L.bufs);
+    const auto o = from_unit<RolloutIO>(io);
+    dispatch_env_prec(L.model, L.integ, L.prec, [&](auto m, auto i, auto pr) {
+        hipLaunchKernelGGL((rollout_step_kernel<decltype(m)::value, decltype(i)::value, decltype(pr)::value, true, 2>),
+                           dim3(L.grid), dim3(rol::Shape<2>::kThreads), 0, (hipStream_t)L.stream, L.state, L.n, L.mode,
+                           p, b, o);
+    });
     return (int)hipGetLastError();
 }
 
 // rr_policy_evaluate's launch (declared in rocket_device.h): eval_kernel<MODEL, INTEG, PREC>, the
-// collect's grid and workgroup. io points to the EvalIO of the calling TU.
-extern "C" int rrc_launch_eval(int model, int integ, int prec, unsigned grid, float* state, uint32_t n, uint32_t mode,
-                               const void* kp, const void* bufs, const void* io, void* stream)
+// collect's grid and workgroup. launch / io point to the EnvLaunch / EvalIO of the calling TU.
+extern "C" int rrc_launch_eval(const void* launch, const void* io)
 {
-    KParams p;
-    Bufs b;
-    EvalIO o;
-    std::memcpy(&p, kp, sizeof(KParams));
-    std::memcpy(&b, bufs, sizeof(Bufs));
-    std::memcpy(&o, io, sizeof(EvalIO));
-    hipStream_t s = (hipStream_t)stream;
-#define RR_EVAL(M, I, PR) \
-    hipLaunchKernelGGL((eval_kernel<M, I, PR>), dim3(grid), dim3(rol::Shape<2>::kThreads), 0, s, state, n, mode, p, b, o)
-#define RR_EVAL_P(M, I)                      \
-    do {                                     \
-        if (prec == 1) RR_EVAL(M, I, 1);     \
-        else if (prec == 2) RR_EVAL(M, I, 2); \
-        else RR_EVAL(M, I, 0);               \
-    } while (0)
-    const bool euler = integ == RR_INT_EULER;
-    if (model == RR_MODEL_6DOF && !euler) RR_EVAL_P(6, RR_INT_RK4);
-    else if (model == RR_MODEL_6DOF) RR_EVAL_P(6, RR_INT_EULER);
-    else if (!euler) RR_EVAL_P(3, RR_INT_RK4);
-    else RR_EVAL_P(3, RR_INT_EULER);
-#undef RR_EVAL_P
-#undef RR_EVAL
+    const auto L = from_unit<EnvLaunch>(launch);
+    const auto p = from_unit<KParams>(L.kp);
+    const auto b = from_unit<Bufs>(L.bufs);
+    const auto o = from_unit<EvalIO>(io);
+    dispatch_env_prec(L.model, L.integ, L.prec, [&](auto m, auto i, auto pr) {
+        hipLaunchKernelGGL((eval_kernel<decltype(m)::value, decltype(i)::value, decltype(pr)::value>), dim3(L.grid),
+                           dim3(rol::Shape<2>::kThreads), 0, (hipStream_t)L.stream, L.state, L.n, L.mode, p, b, o);
+    });
     return (int)hipGetLastError();
 }
 
@@ -144,8 +113,7 @@ extern "C" int rrc_launch_eval(int model, int integ, int prec, unsigned grid, fl
 // (profiles/r06/ppo_vf/)
 extern "C" int rrc_launch_learner(const void* launch, void* stream)
 {
-    PpoLaunch L;
-    std::memcpy(&L, launch, sizeof(PpoLaunch));
+    const auto L = from_unit<PpoLaunch>(launch);
     hipStream_t s = (hipStream_t)stream;
     if (L.op == 2) {
         const dim3 grid((unsigned)((L.a.start[L.a.n] + kAdamThreads - 1) / kAdamThreads));
@@ -176,7 +144,7 @@ extern "C" int rrc_launch_learner(const void* launch, void* stream)
                                L.beta1, L.beta2, L.w1, L.w2, L.eps, L.pack, nx, L.nbp);
         }
     };
-    if (L.obs_dim == 14) run(std::integral_constant<int, 14>{}, std::integral_constant<int, 3>{});
-    else run(std::integral_constant<int, 7>{}, std::integral_constant<int, 2>{});
+    if (L.obs_dim == 14) run(tag<14>{}, tag<3>{});
+    else run(tag<7>{}, tag<2>{});
     return (int)hipGetLastError();
 }

@@ -5,14 +5,18 @@
 // RHS, integrators and ground event, reward and bounds, the obs tile store and the per-env
 // loads / stores that every step kernel inlines (physics_step, store_terminal, store_outputs).
 // Everything here is a template, a forceinline device function, a constant or a plain struct in
-// the anonymous namespace: including it emits no kernel. It also holds the one declaration of
-// each hidden entry point through which the main translation unit reaches the other two.
+// the anonymous namespace: including it emits no kernel. At its end, host side: the variant
+// dispatcher (dispatch_env / dispatch_env_prec: every launch site calls a generic lambda with
+// compile-time tags for the handle's model, integrator and precision), the launch records
+// (EnvLaunch, ExactLaunch) and the one declaration of each hidden entry point through which the main
+// translation unit hands such a record to the other three.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <type_traits>
 
 #include "rocket_hip.h"
@@ -1094,25 +1098,94 @@ static_assert(std::is_trivially_copyable_v<StepIO>, "StepIO crosses TUs by memcp
 
 }  // namespace
 
+// Host side: the one place where a handle's runtime model / integrator / precision picks a kernel
+// instantiation. A launch site passes a generic lambda and reads the template arguments off the
+// compile-time tags it is called with; the arms keep the order in which the kernels were first
+// instantiated (what else a device module holds, and in which order, can change its machine code).
+template <int V>
+using tag = std::integral_constant<int, V>;
+
+// f(tag<PREC>): the policy kernels' PREC 0 (fp32) / 1 (bf16) / 2 (fp16x3)
+template <class F>
+inline void dispatch_prec(int prec, F&& f)
+{
+    if (prec == 1) f(tag<1>{});
+    else if (prec == 2) f(tag<2>{});
+    else f(tag<0>{});
+}
+
+// f(tag<MODEL>, tag<INTEG>) of an RK4 / Euler env
+template <class F>
+inline void dispatch_env(int model, int integ, F&& f)
+{
+    const bool euler = integ == RR_INT_EULER;
+    if (model == RR_MODEL_6DOF && !euler) f(tag<6>{}, tag<RR_INT_RK4>{});
+    else if (model == RR_MODEL_6DOF) f(tag<6>{}, tag<RR_INT_EULER>{});
+    else if (!euler) f(tag<3>{}, tag<RR_INT_RK4>{});
+    else f(tag<3>{}, tag<RR_INT_EULER>{});
+}
+
+// f(tag<MODEL>, tag<INTEG>, tag<PREC>)
+template <class F>
+inline void dispatch_env_prec(int model, int integ, int prec, F&& f)
+{
+    dispatch_env(model, integ, [&](auto m, auto i) { dispatch_prec(prec, [&](auto p) { f(m, i, p); }); });
+}
+
+// f(std::true_type) / f(std::false_type): a kernel's bool template argument
+template <class F>
+inline void dispatch_flag(bool v, F&& f)
+{
+    if (v) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+namespace {
+
+// What the hidden entry points below are handed besides the kernel's own IO struct: one launch of
+// an env kernel of the collect units (rrc_launch_collect / _eval / _eval_trace) ...
+struct EnvLaunch {
+    int model, integ, prec;  // the dispatch_env_prec arm
+    unsigned grid;
+    float* state;
+    uint32_t n, mode;
+    const void *kp, *bufs;   // the caller's KParams / Bufs
+    void* stream;
+};
+// ... and one of an exact-mode step (rrx_launch_exact). variant bit 0: the lean 6DOF kernel,
+// bit 1: [NA][N] action planes
+struct ExactLaunch {
+    int model, variant;
+    unsigned grid;
+    const void* xp;          // XParams on the device
+    const void* bufs;        // the caller's Bufs
+    double* state64;
+    void* stream;
+};
+static_assert(std::is_trivially_copyable_v<EnvLaunch>, "EnvLaunch crosses TUs by memcpy");
+static_assert(std::is_trivially_copyable_v<ExactLaunch>, "ExactLaunch crosses TUs by memcpy");
+
+// a struct of the calling unit, taken over as bytes
+template <class T>
+inline T from_unit(const void* p)
+{
+    T v;
+    std::memcpy(&v, p, sizeof(T));
+    return v;
+}
+
+}  // namespace
+
 // The hidden entry points (not part of the C-ABI) through which the main translation unit launches
 // the kernels compiled in the others. Defined in rocket_exact.hip / rocket_collect.hip /
 // eval_trace/rocket_eval_trace.hip (rrc_launch_eval_trace); the
 // main TU adds weak stand-ins, so that a library built from rocket_hip.hip alone still loads.
-// xp / kp / bufs / io / launch point to the caller's XParams / KParams / Bufs / StepIO, RolloutIO or
-// EvalIO (trace: EvalTraceIO) / PpoLaunch.
+// launch points to the caller's ExactLaunch / EnvLaunch / PpoLaunch, io to its StepIO / RolloutIO /
+// EvalIO, trace to its EvalTraceIO.
 extern "C" {
-__attribute__((visibility("hidden"))) int rrx_launch_exact(int model, int variant, const void* xp, const void* bufs,
-                                                           const void* io, double* state64, unsigned grid,
-                                                           void* stream);
-__attribute__((visibility("hidden"))) int rrc_launch_collect(int model, int integ, int prec, unsigned grid,
-                                                             float* state, uint32_t n, uint32_t mode, const void* kp,
-                                                             const void* bufs, const void* io, void* stream);
-__attribute__((visibility("hidden"))) int rrc_launch_eval(int model, int integ, int prec, unsigned grid, float* state,
-                                                          uint32_t n, uint32_t mode, const void* kp,
-                                                          const void* bufs, const void* io, void* stream);
-__attribute__((visibility("hidden"))) int rrc_launch_eval_trace(int model, int integ, int prec, unsigned grid,
-                                                                float* state, uint32_t n, uint32_t mode,
-                                                                const void* kp, const void* bufs, const void* io,
-                                                                const void* trace, void* stream);
+__attribute__((visibility("hidden"))) int rrx_launch_exact(const void* launch, const void* io);
+__attribute__((visibility("hidden"))) int rrc_launch_collect(const void* launch, const void* io);
+__attribute__((visibility("hidden"))) int rrc_launch_eval(const void* launch, const void* io);
+__attribute__((visibility("hidden"))) int rrc_launch_eval_trace(const void* launch, const void* io, const void* trace);
 __attribute__((visibility("hidden"))) int rrc_launch_learner(const void* launch, void* stream);
 }

@@ -352,36 +352,17 @@ __global__ __launch_bounds__(kBlock) void narrow_kernel(const double* src, float
 
 }  // namespace
 
-// defined by the exact / collect translation units (declared in rocket_device.h); these weak
-// stand-ins (a library built from this file alone, e.g. a tools/ A/B variant) make RR_INT_DOPRI5
-// steps, rr_rollout_collect, rr_policy_evaluate(_trace) and the learner fail loudly instead of failing to load
-extern "C" __attribute__((weak, visibility("hidden"))) int rrx_launch_exact(int, int, const void*, const void*,
-                                                                          const void*, double*, unsigned, void*)
-{
-    return (int)hipErrorInvalidDeviceFunction;
-}
-extern "C" __attribute__((weak, visibility("hidden"))) int rrc_launch_collect(int, int, int, unsigned, float*,
-                                                                            uint32_t, uint32_t, const void*,
-                                                                            const void*, const void*, void*)
-{
-    return (int)hipErrorInvalidDeviceFunction;
-}
-extern "C" __attribute__((weak, visibility("hidden"))) int rrc_launch_eval(int, int, int, unsigned, float*, uint32_t,
-                                                                         uint32_t, const void*, const void*,
-                                                                         const void*, void*)
-{
-    return (int)hipErrorInvalidDeviceFunction;
-}
-extern "C" __attribute__((weak, visibility("hidden"))) int rrc_launch_eval_trace(int, int, int, unsigned, float*,
-                                                                               uint32_t, uint32_t, const void*,
-                                                                               const void*, const void*, const void*,
-                                                                               void*)
-{
-    return (int)hipErrorInvalidDeviceFunction;
-}
-extern "C" __attribute__((weak, visibility("hidden"))) int rrc_launch_learner(const void*, void*)
-{
-    return (int)hipErrorInvalidDeviceFunction;
+// defined by the exact / collect / recording translation units (declared hidden in rocket_device.h);
+// these weak stand-ins (a library built from this file alone, e.g. a tools/ A/B variant) make
+// RR_INT_DOPRI5 steps, rr_rollout_collect, rr_policy_evaluate(_trace) and the learner fail loudly
+// instead of failing to load
+constexpr int kNoUnit = (int)hipErrorInvalidDeviceFunction;
+extern "C" {
+__attribute__((weak)) int rrx_launch_exact(const void*, const void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_collect(const void*, const void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_eval(const void*, const void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_eval_trace(const void*, const void*, const void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_learner(const void*, void*) { return kNoUnit; }
 }
 
 namespace {
@@ -636,6 +617,22 @@ Bufs bufs_of(const rr_env* e)
     return b;
 }
 
+// the kernels' mode word: the handle's flags, and kModeCounter where it keeps counter words (a
+// TimeLimit, episode statistics or the auto-reset's episode count)
+uint32_t mode_of(const rr_env* e)
+{
+    const bool counter = e->p.max_episode_steps > 0 || (e->p.flags & (RR_FLAG_EPISODE_STATS | RR_FLAG_AUTO_RESET));
+    return e->p.flags | (counter ? kModeCounter : 0u);
+}
+
+// the launch record of a rollout / evaluation kernel over the handle's envs (rol::kEnvsPerBlock per
+// workgroup); `b` = bufs_of(e), alive until the launch call returns
+EnvLaunch env_launch(const rr_env* e, int prec, const Bufs* b, void* stream)
+{
+    const unsigned grid = (unsigned)((e->n + rol::kEnvsPerBlock - 1) / rol::kEnvsPerBlock);
+    return {e->p.model, e->p.integrator, prec, grid, e->state, (uint32_t)e->n, mode_of(e), &e->kp, b, stream};
+}
+
 unsigned grid_of(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 int64_t n_words(int64_t n) { return (n + kWave - 1) / kWave; }
 
@@ -888,58 +885,40 @@ int launch_step(rr_env* e, const float* action, float* obs, float* reward, uint8
     io.obs_vec_ok = ((uintptr_t)obs & 15u) == 0;
     const Bufs b = bufs_of(e);
     hipStream_t s = (hipStream_t)stream;
-    const bool m6 = e->p.model == RR_MODEL_6DOF;
-    const bool euler = e->p.integrator == RR_INT_EULER;
+    const bool soa = e->p.flags & RR_FLAG_ACTION_SOA;
     const dim3 grid(grid_of(e->n)), block(kBlock);
     if (e->p.integrator == RR_INT_DOPRI5) {
         // the exact kernels live in the second translation unit (rocket_exact.hip: compiled with a
         // register-pressure-first scheduler, no scratch spills)
-        const int variant = (m6 && e->n > e->exact_lean_min_n ? 1 : 0) | ((e->p.flags & RR_FLAG_ACTION_SOA) ? 2 : 0);
-        const hipError_t xe = (hipError_t)rrx_launch_exact(m6 ? RR_MODEL_6DOF : RR_MODEL_3DOF, variant, e->d_xp, &b,
-                                                           &io, e->state64, grid.x, s);
+        const bool lean = e->p.model == RR_MODEL_6DOF && e->n > e->exact_lean_min_n;
+        const ExactLaunch L = {e->p.model, (lean ? 1 : 0) | (soa ? 2 : 0), grid.x, e->d_xp, &b, e->state64, stream};
+        const hipError_t xe = (hipError_t)rrx_launch_exact(&L, &io);
         if (xe != hipSuccess) return hip_fail(xe, "rr_step: exact launch");
     } else {
         const uint32_t nn = (uint32_t)e->n;
-        const bool counter = e->p.max_episode_steps > 0 || (e->p.flags & (RR_FLAG_EPISODE_STATS | RR_FLAG_AUTO_RESET));
-        const uint32_t mode =
-            e->p.flags | (counter ? kModeCounter : 0u) | (e->n > e->whole_line_min_n ? kModeWholeLines : 0u);
-        const bool soa = e->p.flags & RR_FLAG_ACTION_SOA;
+        const uint32_t mode = mode_of(e) | (e->n > e->whole_line_min_n ? kModeWholeLines : 0u);
         // small N (at most ~2 main waves per SIMD): helper waves draw the reset candidates
         const bool help = (mode & RR_FLAG_AUTO_RESET) && e->n <= e->help_max_n;
         // up to 16 384 envs one main wave per workgroup (64 + 64 threads): the few workgroups
         // spread over 4x as many CUs (A/B at N = 4 096: -5 % 6DOF); above, 4 main waves
         const bool narrow = e->n <= kNarrowMaxN;
-#define RR_LAUNCH(M, I, A)                                                                                          \
-    do {                                                                                                             \
-        if (help && narrow)                                                                                          \
-            hipLaunchKernelGGL((step_kernel<M, I, A, true, 1, ROWS>), dim3((unsigned)((e->n + kWave - 1) / kWave)), \
-                               dim3(2 * kWave), 0, s, e->state, action, nn, mode, e->kp, b, io);                     \
-        else if (help)                                                                                               \
-            hipLaunchKernelGGL((step_kernel<M, I, A, true, kWavesPerBlock, ROWS>), grid, dim3(2 * kBlock), 0, s,     \
-                               e->state, action, nn, mode, e->kp, b, io);                                            \
-        else                                                                                                         \
-            hipLaunchKernelGGL((step_kernel<M, I, A, false, kWavesPerBlock, ROWS>), grid, block, 0, s, e->state,     \
-                               action, nn, mode, e->kp, b, io);                                                      \
-    } while (0)
-        if constexpr (ROWS) {  // row-major actions only (the multi-GPU gather path)
-            if (m6 && !euler) RR_LAUNCH(6, RR_INT_RK4, false);
-            else if (m6) RR_LAUNCH(6, RR_INT_EULER, false);
-            else if (!euler) RR_LAUNCH(3, RR_INT_RK4, false);
-            else RR_LAUNCH(3, RR_INT_EULER, false);
-        } else if (m6 && !euler) {
-            if (soa) RR_LAUNCH(6, RR_INT_RK4, true);
-            else RR_LAUNCH(6, RR_INT_RK4, false);
-        } else if (m6) {
-            if (soa) RR_LAUNCH(6, RR_INT_EULER, true);
-            else RR_LAUNCH(6, RR_INT_EULER, false);
-        } else if (!euler) {
-            if (soa) RR_LAUNCH(3, RR_INT_RK4, true);
-            else RR_LAUNCH(3, RR_INT_RK4, false);
-        } else {
-            if (soa) RR_LAUNCH(3, RR_INT_EULER, true);
-            else RR_LAUNCH(3, RR_INT_EULER, false);
-        }
-#undef RR_LAUNCH
+        dispatch_env(e->p.model, e->p.integrator, [&](auto m, auto i) {
+            constexpr int M = decltype(m)::value, I = decltype(i)::value;
+            auto launch = [&](auto a) {
+                constexpr bool A = decltype(a)::value;
+                if (help && narrow)
+                    hipLaunchKernelGGL((step_kernel<M, I, A, true, 1, ROWS>), dim3((unsigned)n_words(e->n)),
+                                       dim3(2 * kWave), 0, s, e->state, action, nn, mode, e->kp, b, io);
+                else if (help)
+                    hipLaunchKernelGGL((step_kernel<M, I, A, true, kWavesPerBlock, ROWS>), grid, dim3(2 * kBlock), 0, s,
+                                       e->state, action, nn, mode, e->kp, b, io);
+                else
+                    hipLaunchKernelGGL((step_kernel<M, I, A, false, kWavesPerBlock, ROWS>), grid, block, 0, s, e->state,
+                                       action, nn, mode, e->kp, b, io);
+            };
+            if constexpr (ROWS) launch(std::false_type{});  // row-major actions only (the multi-GPU gather path)
+            else dispatch_flag(soa, launch);
+        });
     }
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return hip_fail(err, "rr_step: launch");
@@ -1243,30 +1222,32 @@ int rr_copy_terminal(rr_env* e, float* term_obs, float* term_return, int32_t* te
 
 }  // extern "C"
 
-template <int O, int A, int P>
-struct PolCfg {
-    static constexpr int OBS = O, ACT = A, PREC = P;
-    using L = pol::Layout<O, A, P>;
-};
+// the policy kernels' PREC (0 / 1 / 2) of an RR_POLICY_* value, -1 of anything else
+static int prec_of(int precision)
+{
+    return precision == RR_POLICY_FP32 ? 0 : precision == RR_POLICY_BF16 ? 1 : precision == RR_POLICY_FP16X3 ? 2 : -1;
+}
 
-// f(PolCfg<...>{}) for a supported (obs_dim, act_dim, precision); false otherwise
+// f(tag<OBS>, tag<ACT>, tag<PREC>) for a supported (obs_dim, act_dim, precision); false otherwise
 template <class F>
 static bool pol_dispatch(int obs_dim, int act_dim, int precision, F&& f)
 {
-    if (precision != RR_POLICY_FP32 && precision != RR_POLICY_BF16 && precision != RR_POLICY_FP16X3) return false;
-    if (obs_dim == 14 && act_dim == 3) {
-        if (precision == RR_POLICY_BF16) f(PolCfg<14, 3, 1>{});
-        else if (precision == RR_POLICY_FP16X3) f(PolCfg<14, 3, 2>{});
-        else f(PolCfg<14, 3, 0>{});
-        return true;
-    }
-    if (obs_dim == 7 && act_dim == 2) {
-        if (precision == RR_POLICY_BF16) f(PolCfg<7, 2, 1>{});
-        else if (precision == RR_POLICY_FP16X3) f(PolCfg<7, 2, 2>{});
-        else f(PolCfg<7, 2, 0>{});
-        return true;
-    }
-    return false;
+    const int prec = prec_of(precision);
+    if (prec < 0) return false;
+    if (obs_dim == 14 && act_dim == 3) dispatch_prec(prec, [&](auto p) { f(tag<14>{}, tag<3>{}, p); });
+    else if (obs_dim == 7 && act_dim == 2) dispatch_prec(prec, [&](auto p) { f(tag<7>{}, tag<2>{}, p); });
+    else return false;
+    return true;
+}
+
+// the checks every policy-driven env launch shares, after the caller's null checks: `params`
+// 16-B aligned and a known precision. Returns the kernels' PREC, or fails with `w`'s prefix (< 0)
+static int policy_prec(const std::string& w, const float* params, int precision)
+{
+    if (((uintptr_t)params & 15) != 0) return fail(RR_EINVAL, w + "params must be 16-B aligned");
+    if (prec_of(precision) < 0)
+        return fail(RR_EINVAL, w + "precision must be RR_POLICY_FP32, RR_POLICY_BF16 or RR_POLICY_FP16X3");
+    return prec_of(precision);
 }
 
 #define RR_POL_UNSUPPORTED(fn) \
@@ -1277,8 +1258,8 @@ extern "C" {
 int rr_policy_layout(int obs_dim, int act_dim, int precision, int64_t* off)
 {
     int size = 0;
-    const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto c) {
-        using LL = typename decltype(c)::L;
+    const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto o, auto a, auto p) {
+        using LL = pol::Layout<decltype(o)::value, decltype(a)::value, decltype(p)::value>;
         if (off) {
             const int64_t v[12] = {LL::L1A, LL::B1, LL::L2A, LL::B2, LL::TOWER, LL::PI,
                                    LL::VF,  LL::HA, LL::HV,  LL::HB, LL::VB,    LL::LS};
@@ -1298,10 +1279,10 @@ int rr_policy_pack(int obs_dim, int act_dim, int precision, const float* const* 
         ps.p[k] = src[k];
     }
     hipStream_t s = (hipStream_t)stream;
-    const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto c) {
-        using C = decltype(c);
-        hipLaunchKernelGGL((policy_pack_kernel<C::OBS, C::ACT, C::PREC>), dim3((C::L::SIZE + 255) / 256), dim3(256),
-                           0, s, ps, params);
+    const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto o, auto a, auto p) {
+        constexpr int O = decltype(o)::value, A = decltype(a)::value, P = decltype(p)::value;
+        hipLaunchKernelGGL((policy_pack_kernel<O, A, P>), dim3((pol::Layout<O, A, P>::SIZE + 255) / 256), dim3(256), 0,
+                           s, ps, params);
     });
     if (!ok) return RR_POL_UNSUPPORTED("rr_policy_pack");
     hipError_t err = hipGetLastError();
@@ -1326,11 +1307,11 @@ int rr_policy_act(const float* params, int obs_dim, int act_dim, int precision, 
     // made seed 1 give env e the stream seed 0 gives env e ^ 1, and seed 2^32 that of iteration + 1)
     const uint64_t mixed = splitmix64(seed);
     const uint32_t lo = (uint32_t)mixed, hi = (uint32_t)(mixed >> 32);
-    const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto c) {
-        using C = decltype(c);
-        hipLaunchKernelGGL((policy_act_kernel<C::OBS, C::ACT, C::PREC>), grid, block, 0, s, params, n, env_id_offset,
-                           obs, lo, hi, iter, (uint32_t)t, action_env, action, value, log_prob, obs_copy,
-                           prev_term_obs, prev_truncated, prev_reward, gamma, reward_out, done, start_out);
+    const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto o, auto a, auto p) {
+        hipLaunchKernelGGL((policy_act_kernel<decltype(o)::value, decltype(a)::value, decltype(p)::value>), grid,
+                           block, 0, s, params, n, env_id_offset, obs, lo, hi, iter, (uint32_t)t, action_env, action,
+                           value, log_prob, obs_copy, prev_term_obs, prev_truncated, prev_reward, gamma, reward_out,
+                           done, start_out);
     });
     if (!ok) return RR_POL_UNSUPPORTED("rr_policy_act");
     hipError_t err = hipGetLastError();
@@ -1349,10 +1330,10 @@ int rr_policy_bootstrap(const float* params, int obs_dim, int act_dim, int preci
     if (((uintptr_t)params & 15) != 0) return fail(RR_EINVAL, "rr_policy_bootstrap: params must be 16-B aligned");
     const dim3 grid((unsigned)((n + pol::kEnvsPerBlock - 1) / pol::kEnvsPerBlock)), block(pol::kThreads);
     hipStream_t s = (hipStream_t)stream;
-    const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto c) {
-        using C = decltype(c);
-        hipLaunchKernelGGL((policy_bootstrap_kernel<C::OBS, C::ACT, C::PREC>), grid, block, 0, s, params, n,
-                           term_obs, truncated, reward, gamma, reward_out, obs, value_out);
+    const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto o, auto a, auto p) {
+        hipLaunchKernelGGL((policy_bootstrap_kernel<decltype(o)::value, decltype(a)::value, decltype(p)::value>),
+                           grid, block, 0, s, params, n, term_obs, truncated, reward, gamma, reward_out, obs,
+                           value_out);
     });
     if (!ok) return RR_POL_UNSUPPORTED("rr_policy_bootstrap");
     hipError_t err = hipGetLastError();
@@ -1363,15 +1344,14 @@ namespace {
 int launch_rollout(rr_env* e, const char* who, bool multi, const float* params, int precision, uint64_t seed,
                    const uint64_t* iter, RolloutIO& io, void* stream)
 {
+    const std::string w = std::string(who) + ": ";
     if (!params || !iter || !io.buf_obs || !io.buf_act || !io.buf_val || !io.buf_logp || !io.buf_start ||
         !io.buf_rew || !io.reward || !io.done)
-        return fail(RR_EINVAL, std::string(who) + ": null argument");
-    if (((uintptr_t)params & 15) != 0) return fail(RR_EINVAL, std::string(who) + ": params must be 16-B aligned");
-    if (precision != RR_POLICY_FP32 && precision != RR_POLICY_BF16 && precision != RR_POLICY_FP16X3)
-        return fail(RR_EINVAL,
-                    std::string(who) + ": precision must be RR_POLICY_FP32, RR_POLICY_BF16 or RR_POLICY_FP16X3");
+        return fail(RR_EINVAL, w + "null argument");
+    const int prec = policy_prec(w, params, precision);
+    if (prec < 0) return prec;
     if (e->p.integrator == RR_INT_DOPRI5)
-        return fail(RR_EINVAL, std::string(who) + ": RR_INT_DOPRI5 envs step through rr_policy_act + rr_step");
+        return fail(RR_EINVAL, w + "RR_INT_DOPRI5 envs step through rr_policy_act + rr_step");
     io.params = params;
     io.iter = iter;
     const uint64_t mixed = splitmix64(seed);  // as rr_policy_act: the same noise key
@@ -1380,10 +1360,7 @@ int launch_rollout(rr_env* e, const char* who, bool multi, const float* params, 
     io.obs_vec_ok = ((uintptr_t)io.obs & 15u) == 0;
     io.buf_obs_vec_ok = ((uintptr_t)io.buf_obs & 15u) == 0;
     const Bufs b = bufs_of(e);
-    const uint32_t nn = (uint32_t)e->n;
-    const bool counter = e->p.max_episode_steps > 0 || (e->p.flags & (RR_FLAG_EPISODE_STATS | RR_FLAG_AUTO_RESET));
-    const uint32_t mode = e->p.flags | (counter ? kModeCounter : 0u);
-    const dim3 grid((unsigned)((e->n + rol::kEnvsPerBlock - 1) / rol::kEnvsPerBlock));
+    const EnvLaunch L = env_launch(e, prec, &b, stream);
     // 64 envs per wave (two 32-env MFMA column tiles). 32 envs per wave (rol::Shape<1>, two waves
     // per SIMD) measured 2-16 % slower at N = 65536 in round 2 and 4-8 % slower in round 4, with or
     // without the second wave's start staggered: the env step's VALU work doubles, and an fp32
@@ -1391,44 +1368,28 @@ int launch_rollout(rr_env* e, const char* who, bool multi, const float* params, 
     // (tools/coissue_probe.hip, profiles/r04/coissue/).
     // The collect kernel (MULTI) lives in the third translation unit (rocket_collect.hip), compiled
     // with the MFMA accumulators in VGPRs (rl_rocket_amd/build.py COLLECT_FLAGS).
-    hipStream_t s = (hipStream_t)stream;
-    const int prec = precision == RR_POLICY_BF16 ? 1 : precision == RR_POLICY_FP16X3 ? 2 : 0;
     hipError_t err = hipSuccess;
     if (multi) {
-        err = (hipError_t)rrc_launch_collect(e->p.model, e->p.integrator, prec, grid.x, e->state, nn, mode, &e->kp,
-                                             &b, &io, stream);
+        err = (hipError_t)rrc_launch_collect(&L, &io);
     } else {
-        const bool m6 = e->p.model == RR_MODEL_6DOF, euler = e->p.integrator == RR_INT_EULER;
-#define RR_LAUNCH(M, I, PR)                                                                                     \
-    hipLaunchKernelGGL((rollout_step_kernel<M, I, PR, false, 2>), grid, dim3(rol::Shape<2>::kThreads), 0, s, \
-                       e->state, nn, mode, e->kp, b, io)
-#define RR_LAUNCH_P(M, I)                  \
-    do {                                   \
-        if (prec == 1) RR_LAUNCH(M, I, 1); \
-        else if (prec == 2) RR_LAUNCH(M, I, 2); \
-        else RR_LAUNCH(M, I, 0);           \
-    } while (0)
-        if (m6 && !euler) RR_LAUNCH_P(6, RR_INT_RK4);
-        else if (m6) RR_LAUNCH_P(6, RR_INT_EULER);
-        else if (!euler) RR_LAUNCH_P(3, RR_INT_RK4);
-        else RR_LAUNCH_P(3, RR_INT_EULER);
-#undef RR_LAUNCH_P
-#undef RR_LAUNCH
+        dispatch_env_prec(L.model, L.integ, L.prec, [&](auto m, auto i, auto p) {
+            constexpr int M = decltype(m)::value, I = decltype(i)::value, P = decltype(p)::value;
+            hipLaunchKernelGGL((rollout_step_kernel<M, I, P, false, 2>), dim3(L.grid), dim3(rol::Shape<2>::kThreads),
+                               0, (hipStream_t)stream, e->state, L.n, L.mode, e->kp, b, io);
+        });
         err = hipGetLastError();
     }
-    if (err != hipSuccess) return hip_fail(err, (std::string(who) + ": launch").c_str());
+    if (err != hipSuccess) return hip_fail(err, (w + "launch").c_str());
     e->steps += io.T;
     note_stream(e, stream);
     return RR_OK;
 }
-}  // namespace
 
-int rr_rollout_step(rr_env* e, const float* params, int precision, uint64_t seed, const uint64_t* iter, int t,
-                    float gamma, float* buf_obs, float* buf_action, float* buf_value, float* buf_log_prob,
-                    float* buf_start, float* buf_reward, float* obs, float* reward, uint8_t* done, uint8_t* truncated,
-                    float* terms, void* stream)
+// the RolloutIO fields rr_rollout_step and rr_rollout_collect both take from their caller (the
+// per-step buffer slices and the env outputs); the rest zero
+RolloutIO rollout_io(float* buf_obs, float* buf_action, float* buf_value, float* buf_log_prob, float* buf_start,
+                     float* buf_reward, float* obs, float* reward, uint8_t* done, uint8_t* truncated, float* terms)
 {
-    if (!e) return fail(RR_EINVAL, "rr_rollout_step: null handle");
     RolloutIO io = {};
     io.buf_obs = buf_obs;
     io.buf_act = buf_action;
@@ -1441,6 +1402,18 @@ int rr_rollout_step(rr_env* e, const float* params, int precision, uint64_t seed
     io.done = done;
     io.truncated = truncated;
     io.terms = terms;
+    return io;
+}
+}  // namespace
+
+int rr_rollout_step(rr_env* e, const float* params, int precision, uint64_t seed, const uint64_t* iter, int t,
+                    float gamma, float* buf_obs, float* buf_action, float* buf_value, float* buf_log_prob,
+                    float* buf_start, float* buf_reward, float* obs, float* reward, uint8_t* done, uint8_t* truncated,
+                    float* terms, void* stream)
+{
+    if (!e) return fail(RR_EINVAL, "rr_rollout_step: null handle");
+    RolloutIO io = rollout_io(buf_obs, buf_action, buf_value, buf_log_prob, buf_start, buf_reward, obs, reward, done,
+                              truncated, terms);
     io.t = (uint32_t)t;
     io.gamma = gamma;
     io.T = 1;
@@ -1458,23 +1431,13 @@ int rr_rollout_collect(rr_env* e, const float* params, int precision, uint64_t s
     if (n_steps <= 0) return fail(RR_EINVAL, "rr_rollout_collect: n_steps must be positive");
     if ((buf_advantage == nullptr) != (buf_return == nullptr))
         return fail(RR_EINVAL, "rr_rollout_collect: buf_advantage and buf_return go together");
-    RolloutIO io = {};
-    io.buf_obs = buf_obs;
-    io.buf_act = buf_action;
-    io.buf_val = buf_value;
-    io.buf_logp = buf_log_prob;
-    io.buf_start = buf_start;
-    io.buf_rew = buf_reward;
+    RolloutIO io = rollout_io(buf_obs, buf_action, buf_value, buf_log_prob, buf_start, buf_reward, obs, reward, done,
+                              truncated, terms);
     io.buf_adv = buf_advantage;
     io.buf_ret = buf_return;
     io.last_value = last_value;
     io.last_done = last_done;
     io.last_start = last_start;
-    io.obs = obs;
-    io.reward = reward;
-    io.done = done;
-    io.truncated = truncated;
-    io.terms = terms;
     io.t = 0;
     io.T = (uint32_t)n_steps;
     io.gamma = (float)gamma;  // the timeout bootstrap, fp32 as rr_rollout_step's
@@ -1494,9 +1457,8 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
     if (!e) return fail(RR_EINVAL, w + "null handle");
     if (!params || !out || !out->episodes)
         return fail(RR_EINVAL, w + "params, out and out->episodes must not be null");
-    if (((uintptr_t)params & 15) != 0) return fail(RR_EINVAL, w + "params must be 16-B aligned");
-    if (precision != RR_POLICY_FP32 && precision != RR_POLICY_BF16 && precision != RR_POLICY_FP16X3)
-        return fail(RR_EINVAL, w + "precision must be RR_POLICY_FP32, RR_POLICY_BF16 or RR_POLICY_FP16X3");
+    const int prec = policy_prec(w, params, precision);
+    if (prec < 0) return prec;
     // the trace's own checks come before anything reads the handle
     if (traced) {
         if (!trace) return fail(RR_EINVAL, w + "trace must not be null");
@@ -1526,9 +1488,7 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
     io.n_episodes = n_episodes;
     io.obs_vec_ok = ((uintptr_t)obs & 15u) == 0;
     const Bufs b = bufs_of(e);
-    const uint32_t mode = e->p.flags | kModeCounter;  // an auto-reset handle keeps counter words
-    const unsigned grid = (unsigned)((e->n + rol::kEnvsPerBlock - 1) / rol::kEnvsPerBlock);
-    const int prec = precision == RR_POLICY_BF16 ? 1 : precision == RR_POLICY_FP16X3 ? 2 : 0;
+    const EnvLaunch L = env_launch(e, prec, &b, stream);  // an auto-reset handle: its mode has kModeCounter
     // compiled in the collect translation unit (rocket_collect.hip), as the collect kernel they derive from
     hipError_t err;
     if (traced) {
@@ -1540,11 +1500,9 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
         t.length = trace->length;
         t.n_slots = trace->n_slots;
         t.steps = trace->steps;
-        err = (hipError_t)rrc_launch_eval_trace(e->p.model, e->p.integrator, prec, grid, e->state, (uint32_t)e->n, mode,
-                                                &e->kp, &b, &io, &t, stream);
+        err = (hipError_t)rrc_launch_eval_trace(&L, &io, &t);
     } else {
-        err = (hipError_t)rrc_launch_eval(e->p.model, e->p.integrator, prec, grid, e->state, (uint32_t)e->n, mode,
-                                          &e->kp, &b, &io, stream);
+        err = (hipError_t)rrc_launch_eval(&L, &io);
     }
     if (err != hipSuccess) return hip_fail(err, (w + "launch").c_str());
     note_stream(e, stream);

@@ -78,8 +78,8 @@ def _flags(done_kind):
 
 
 @functools.lru_cache(maxsize=None)
-def _reference(model, prec, n, landing=False):
-    """Handle A: NE * TL rr_rollout_step launches, read back after every step. Returns the rows the
+def _reference(model, prec, n, landing=False, tl=TL, integrator="rk4"):
+    """Handle A: NE * tl rr_rollout_step launches, read back after every step. Returns the rows the
     evaluation must write, A's snapshot (state, v0, counter, return) at the step each env's last
     episode ended (its final snapshot where it did not finish), the snapshots after the steps in
     KEEP, and the step of the first done. Never modified by the tests that share it."""
@@ -88,7 +88,7 @@ def _reference(model, prec, n, landing=False):
     from rl_rocket_amd.batch import _ptr
     from rl_rocket_amd.rollout import PolicyPack
 
-    a = _batch(model, n, landing)
+    a = _batch(model, n, landing, max_episode_steps=tl, integrator=integrator)
     pol = _policy(model)
     ns, na, nt = a.state_dim, a.action_dim, a.n_terms
     pack = PolicyPack(pol, ns, na, a.device, precision=prec)
@@ -104,7 +104,7 @@ def _reference(model, prec, n, landing=False):
     m_first = a.get_state()[0][-1].clone()
     last = [t.clone() for t in _aux(a)]
     kept, first_done = {}, None
-    for t in range(NE * TL):
+    for t in range(NE * tl):
         stream = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
         _lib.check(lib.rr_rollout_step(a._h, _ptr(params), pack.prec, 11, _ptr(it), t, 0.99, *[_ptr(b) for b in bufs],
                                        _ptr(a.obs), _ptr(a.reward), _ptr(a.done), _ptr(a.truncated), _ptr(a.terms),
@@ -136,13 +136,14 @@ def _reference(model, prec, n, landing=False):
     return ref
 
 
-def _evaluate(model, prec, n, landing=False, max_steps=NE * TL, fused=None, policy=None):
+def _evaluate(model, prec, n, landing=False, max_steps=NE * TL, fused=None, policy=None, record=None, **over):
+    """Handle B: one evaluation into sentinel-filled outputs (`record`: a recording one; `over`: _batch's)."""
     import torch
     from rl_rocket_amd.rollout import PolicyEvaluator
 
-    b = _batch(model, n, landing)
+    b = _batch(model, n, landing, **over)
     ev = PolicyEvaluator(b, policy if policy is not None else _policy(model), n_episodes=NE, max_steps=max_steps,
-                         policy_dtype=prec, fused=fused)
+                         policy_dtype=prec, fused=fused, record=record)
     for t, v in ((ev.ep_return, SENT), (ev.ep_length, -7), (ev.flags, 0xEE), (ev.used_mass, SENT),
                  (ev.final_state, SENT), (ev.episodes, -7)):
         t.fill_(v)

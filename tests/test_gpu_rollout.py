@@ -244,27 +244,21 @@ def test_fused_collect_matches_semantics(fused, prec):
     env.close()
 
 
-@pytest.mark.parametrize("prec,T", [("fp32", 8), ("bf16", 8), ("fp16x3", 8), ("fp32", 37)])
-@pytest.mark.parametrize("model", [6, 3])
-def test_one_launch_rollout_bitwise_equals_two_launch(model, prec, T):
-    """rr_rollout_collect (the whole rollout + GAE in one kernel) and rr_rollout_step (policy +
-    env step in one kernel per step) against rr_policy_act + rr_step: every rollout buffer,
-    the env outputs (incl. reward terms), the terminal rows and the env state bitwise equal
-    over two collects (TimeLimit 6 < n_steps: truncation bootstraps and auto-resets inside the
-    rollout; ragged N: idle waves in the last workgroup; n_steps 37: the collect kernel's GAE
-    scan runs in 16-step chunks, 16 + 16 + 5)."""
+def three_rollout_paths_agree(model, prec, T, n, integrator="rk4"):
+    """The body of test_one_launch_rollout_bitwise_equals_two_launch (tests/test_gpu_dispatch.py runs
+    it for every integrator and precision at a small n)."""
     import torch
     from rl_rocket_amd.batch import RocketBatch
     from rl_rocket_amd.params import ENV_CONFIG_6DOF
     from rl_rocket_amd.rollout import DeviceRollout
 
-    n = 4096 + 37
     ns, na = (14, 3) if model == 6 else (7, 2)
     kw = ENV_CONFIG_6DOF if model == 6 else {}
     pol = _policy(ns, na, seed=3)
     ros = []
     for one, per_step in ((False, True), (True, True), (True, False)):
-        env = RocketBatch(n, model=model, device="cuda:0", max_episode_steps=6, compute_terms=True, **kw)
+        env = RocketBatch(n, model=model, device="cuda:0", max_episode_steps=6, compute_terms=True,
+                          integrator=integrator, **kw)
         ro = DeviceRollout(env, pol, n_steps=T, policy_dtype=prec, one_launch=one, per_step=per_step, seed=11)
         assert ro.one_launch == one and ro.per_step == per_step
         ros.append(ro)
@@ -289,6 +283,18 @@ def test_one_launch_rollout_bitwise_equals_two_launch(model, prec, T):
     assert a.starts[1:].sum() > 0 and (a.rewards != 0).any()
     for ro in ros:
         ro.env.close()
+
+
+@pytest.mark.parametrize("prec,T", [("fp32", 8), ("bf16", 8), ("fp16x3", 8), ("fp32", 37)])
+@pytest.mark.parametrize("model", [6, 3])
+def test_one_launch_rollout_bitwise_equals_two_launch(model, prec, T):
+    """rr_rollout_collect (the whole rollout + GAE in one kernel) and rr_rollout_step (policy +
+    env step in one kernel per step) against rr_policy_act + rr_step: every rollout buffer,
+    the env outputs (incl. reward terms), the terminal rows and the env state bitwise equal
+    over two collects (TimeLimit 6 < n_steps: truncation bootstraps and auto-resets inside the
+    rollout; ragged N: idle waves in the last workgroup; n_steps 37: the collect kernel's GAE
+    scan runs in 16-step chunks, 16 + 16 + 5)."""
+    three_rollout_paths_agree(model, prec, T, n=4096 + 37)
 
 
 def test_rollout_collect_full_size_configs4():
