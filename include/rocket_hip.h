@@ -500,7 +500,9 @@ int rr_clip_adam(int n_tensors, float* const* params, float* const* grads, float
  * A call with flags & RR_PPO_CHAINED skips the packing / statistics launch and uses what the
  * previous rr_ppo_update on the same workspace left there. That previous call must have been
  * given next_idx = this idx, next_batch = this batch, and nothing else may have written the
- * parameters since. Without the flag the call packs from the parameters itself (four launches).
+ * parameters since. Its batch may be smaller than the previous call's (a short last minibatch):
+ * what is handed over sits at workspace offsets that do not depend on batch, on a workspace sized
+ * for the largest batch. Without the flag the call packs from the parameters itself (four launches).
  * Arithmetic as the two calls, except that the clip's norm sums the squares in the finish's
  * order. workspace: device, 16-B aligned, rr_ppo_update_workspace_size bytes; lr a device float. */
 #define RR_PPO_CHAINED 0x1u

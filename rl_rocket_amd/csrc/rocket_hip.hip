@@ -1556,15 +1556,18 @@ int64_t ppo_pack_floats(int obs_dim, int act_dim)
     return obs_dim == 14 ? ppo::Pack<14, 3>::SIZE : ppo::Pack<7, 2>::SIZE;
 }
 
-// rr_ppo_workspace_size's layout: advantage partial sums | 2 towers x nwg partial-gradient vectors |
-// 2 packed tower images (16-B aligned: Part::SIZE % 4 == 0)
+// rr_ppo_workspace_size's layout: advantage partial sums | 2 packed tower images | 2 towers x nwg
+// partial-gradient vectors (16-B aligned: Pack::SIZE % 4 == 0). What one rr_ppo_update call leaves
+// for the next, chained one (the advantage sums, the packed images) sits ahead of the only section
+// whose size follows the call's batch: a chained call with a shorter minibatch, and so fewer
+// workgroups, finds both where the call before it wrote them.
 void ppo_carve(PpoLaunch& L, int obs_dim, int act_dim, int64_t batch, void* workspace)
 {
     L.obs_dim = obs_dim;
     L.nwg = (int)ppo_nwg(batch);
     L.adv_part = (double*)workspace;
-    L.part = (float*)((char*)workspace + 2 * ppo::kAdvPart * sizeof(double));
-    L.pack = L.part + 2 * (int64_t)L.nwg * ppo_part_floats(obs_dim, act_dim);
+    L.pack = (float*)((char*)workspace + 2 * ppo::kAdvPart * sizeof(double));
+    L.part = L.pack + 2 * ppo_pack_floats(obs_dim, act_dim);
 }
 }  // namespace
 
@@ -1618,7 +1621,7 @@ int rr_ppo_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* byte
     const int64_t pf = ppo_part_floats(obs_dim, act_dim);
     if (!pf) return fail(RR_EINVAL, "rr_ppo_workspace_size: supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
     if (batch < 2 || !bytes) return fail(RR_EINVAL, "rr_ppo_workspace_size: batch >= 2 and bytes required");
-    // adv partial sums | 2 towers x nwg partial-gradient vectors | 2 packed tower images
+    // adv partial sums | 2 packed tower images | 2 towers x nwg partial-gradient vectors
     *bytes = (int64_t)(2 * ppo::kAdvPart * sizeof(double)) +
              2 * (ppo_nwg(batch) * pf + ppo_pack_floats(obs_dim, act_dim)) * (int64_t)sizeof(float);
     return RR_OK;

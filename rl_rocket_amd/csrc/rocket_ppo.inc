@@ -4,7 +4,8 @@
 // Computes, for one minibatch of a device rollout, the gradients that stable_baselines3 1.6
 // PPO.train's loss.backward() produces for the MlpPolicy actor-critic (the reference trains
 // PPO("MlpPolicy", ..., ent_coef=0.01), main_6DOF.py:62-69; SB3's defaults otherwise):
-//   A   = (adv - mean(adv)) / (std(adv) + 1e-8)                      (normalize_advantage)
+//   A   = (adv - mean(adv)) / (std(adv) + 1e-8)                      (normalize_advantage; mean and
+//         std from fp64 sums, the mean subtracted as a float pair: no rounding of a large mean)
 //   r   = exp(log_prob(a) - old_log_prob)
 //   pg  = -mean(min(A r, A clamp(r, 1 - clip, 1 + clip)))
 //   vf  = mean((ret - V)^2)                                         (clip_range_vf None)
@@ -312,7 +313,8 @@ __device__ __forceinline__ void ppo_grad_tower(
     }
     for (int k = lane; k < (32 - OBS) * TS; k += kWave) XT[OBS * TS + k] = k < TS ? 1.0f : 0.0f;
     // minibatch advantage statistics (pi): mean, unbiased std
-    float a_mean = 0.0f, a_den = 1.0f;
+    // (the mean as a float pair: rounded to one float, a mean of 50 over a std of 0.5 moves every A by ~3e-6)
+    float a_mean = 0.0f, a_mean_lo = 0.0f, a_den = 1.0f;
     if (tw == 0) {
         double s = 0.0, q = 0.0;
 #pragma unroll
@@ -325,6 +327,7 @@ __device__ __forceinline__ void ppo_grad_tower(
         const double n = (double)bs, mean = s / n;
         const double var = (q - s * mean) / (n - 1.0);
         a_mean = (float)mean;
+        a_mean_lo = (float)(mean - (double)a_mean);
         a_den = sqrtf((float)(var > 0.0 ? var : 0.0)) + 1e-8f;
     }
     __syncthreads();
@@ -377,7 +380,7 @@ __device__ __forceinline__ void ppo_grad_tower(
         // heads and the per-sample loss derivatives (both lane halves hold sample j)
         float dh[ACT];
         if (tw == 0) {
-            const float A = valid ? (in.av - a_mean) / a_den : 0.0f;
+            const float A = valid ? ((in.av - a_mean) - a_mean_lo) / a_den : 0.0f;
             float lp = 0.0f, d[ACT];
 #pragma unroll
             for (int a = 0; a < ACT; ++a) {
@@ -604,8 +607,8 @@ __device__ __forceinline__ void ppo_grad_tower(
                             (a.w + b.w) + (c.w + d.w));
     }
     RR_ST(11);
-    // (diagnostic builds) past the packed images: 16 floats per wave, in a workspace the caller enlarged
-    RR_ACC_WRITE(part + 2 * (int64_t)gridDim.x * PT::SIZE + 2 * K::SIZE,
+    // (diagnostic builds) past the partial vectors: 16 floats per wave, in a workspace the caller enlarged
+    RR_ACC_WRITE(part + 2 * (int64_t)gridDim.x * PT::SIZE,
                  (((int64_t)tw * gridDim.x + blockIdx.x) * ppo::kWaves + wv) * 16, (uint32_t)lane, true);
 }
 

@@ -5,68 +5,16 @@ SB3 1.6 PPO.train) evaluated in float64 on the same parameters and minibatch.
 Tolerance: per gradient tensor, max |fused - fp64| <= 1e-4 * max |fp64| + 1e-7 (fp32 sums over
 up to 65 536 samples in another order, tanh via exp2 / rcp: the PyTorch fp32 autograd of the same
 loss lands at the same level, printed beside it). Stats (policy_loss, value_loss, entropy,
-clip_fraction, approx_kl) within 1e-5 relative + 1e-6 (clip_fraction: within 2 samples)."""
+clip_fraction, approx_kl) within 1e-5 relative + 1e-6 (clip_fraction: within 2 samples).
+The inputs and the reference are tests/ppo_ref.py's, shared with tests/test_gpu_ppo_edges.py."""
 import copy
 import types
 
 import pytest
 
+from ppo_ref import NAMES, reference as _reference, setup as _setup
+
 pytestmark = pytest.mark.gpu
-
-
-def _setup(ns, na, n, seed=0):
-    import torch
-    from rl_rocket_amd.rollout import MlpActorCritic
-
-    g = torch.Generator("cuda:0").manual_seed(seed)
-    torch.manual_seed(seed)
-    pol = MlpActorCritic(ns, na).cuda()
-    with torch.no_grad():  # off SB3's small-gain init so every weight and bias matters
-        for p in pol.parameters():
-            p.add_(0.2 * torch.randn(p.shape, device="cuda:0", generator=g))
-    f = dict(device="cuda:0", dtype=torch.float32)
-    obs = 0.7 * torch.randn((n, ns), generator=g, **f)
-    act = torch.randn((n, na), generator=g, **f)
-    with torch.no_grad():
-        mean, _ = pol(obs)
-        old_lp = pol.log_prob(mean, act) + 0.25 * torch.randn((n,), generator=g, **f)  # ratios on both sides of the clip
-    adv = 2.0 * torch.randn((n,), generator=g, **f) + 0.3
-    ret = 5.0 * torch.randn((n,), generator=g, **f)
-    ro = types.SimpleNamespace(n_steps=1, env=types.SimpleNamespace(num_envs=n, state_dim=ns, action_dim=na),
-                               obs=obs.view(1, n, ns), actions=act.view(1, n, na), log_probs=old_lp.view(1, n),
-                               advantages=adv.view(1, n), returns=ret.view(1, n))
-    return pol, ro, g
-
-
-def _reference(pol, ro, idx, dtype, clip=0.2, ent_coef=0.01, vf_coef=0.5):
-    """ppo_update's loss for one minibatch (autograd) in `dtype`."""
-    import torch
-    from rl_rocket_amd.rollout import _policy_tensors
-
-    p = copy.deepcopy(pol).to(dtype)
-    n = ro.env.num_envs
-    obs = ro.obs.reshape(n, -1)[idx].to(dtype)
-    act = ro.actions.reshape(n, -1)[idx].to(dtype)
-    old = ro.log_probs.reshape(n)[idx].to(dtype)
-    adv = ro.advantages.reshape(n)[idx].to(dtype)
-    ret = ro.returns.reshape(n)[idx].to(dtype)
-    mean, value = p(obs)
-    lp = p.log_prob(mean, act)
-    adv = (adv - adv.mean()) / (adv.std() + 1e-8)
-    ratio = torch.exp(lp - old)
-    pg = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - clip, 1 + clip)).mean()
-    vf = torch.nn.functional.mse_loss(ret, value)
-    ent = -p.entropy(len(idx)).mean()
-    (pg + ent_coef * ent + vf_coef * vf).backward()
-    with torch.no_grad():
-        lr = lp - old
-        stats = [pg.item(), vf.item(), -ent.item(), ((ratio - 1).abs() > clip).double().mean().item(),
-                 ((torch.exp(lr) - 1) - lr).mean().item()]
-    return [t.grad.double() for t in _policy_tensors(p)], stats
-
-
-NAMES = ["pi.W1", "pi.b1", "pi.W2", "pi.b2", "vf.W1", "vf.b1", "vf.W2", "vf.b2", "W_action", "b_action",
-         "W_value", "b_value", "log_std"]
 
 
 @pytest.mark.parametrize("ns,na", [(14, 3), (7, 2)])
@@ -324,11 +272,27 @@ def test_fused_update_with_the_shipped_adam_tracks_autograd():
 def test_fused_update_refuses_a_one_row_remainder_before_stepping():
     """ppo_update(fused=True) with n_steps * num_envs % batch_size == 1 raises before the first
     minibatch (the policy and optimizer are untouched); a remainder of >= 2 rows is a valid last
-    minibatch."""
+    minibatch, and the epoch that ends in it (minibatches of 3999, 3999 and 2 rows: 32, 32 and 1
+    workgroups per tower, the last two calls chained) lands within 1e-6 of the PyTorch-autograd
+    ppo_update from the same state with the same generator. That comparison runs on copies under
+    Adam(lr 1e-3, eps 1.0), the setting of every 1e-6 bar between the two paths here: with it a
+    step is proportional to the gradient, while at eps 1e-5 a gradient element near 0 may step the
+    other way by 2 lr (test_fused_update_with_the_shipped_adam_tracks_autograd)."""
     import torch
     from rl_rocket_amd.rollout import ppo_update
 
     env, pol, ro = _rollout_for_update(n=1000, T=8)  # 8000 rows
+    pols = [copy.deepcopy(pol) for _ in range(2)]
+    opts = [torch.optim.Adam(p.parameters(), lr=1e-3, eps=1.0, capturable=True) for p in pols]
+    gen = lambda: torch.Generator("cuda:0").manual_seed(17)  # noqa: E731
+    ppo_update(pols[0], opts[0], ro, n_epochs=1, batch_size=3999, generator=gen())
+    ppo_update(pols[1], opts[1], ro, n_epochs=1, batch_size=3999, generator=gen(), fused=True)
+    torch.cuda.synchronize()
+    moved = max((x - y).abs().max().item() for x, y in zip(pol.parameters(), pols[0].parameters()))
+    worst = max((x - y).abs().max().item() for x, y in zip(pols[0].parameters(), pols[1].parameters()))
+    print("2-row remainder: moved %.3e, fused vs autograd %.3e" % (moved, worst))
+    assert moved > 1e-5
+    assert worst <= 1e-6, worst
     opt = torch.optim.Adam(pol.parameters(), lr=3e-4, eps=1e-5, capturable=True)
     before = [p.detach().clone() for p in pol.parameters()]
     with pytest.raises(ValueError):

@@ -1,7 +1,7 @@
 """Phase breakdown of the PPO gradient kernel (ppo_grad_kernel) from a diagnostic build
 (RR_DIAG_STAMPS: per-wave s_memtime cycles of 12 phases, the tile-loop phases summed over the
-wave's tiles; rocket_ppo.inc). The kernel writes them past the packed tower images, so this tool
-enlarges PPOGrad's workspace by that much.
+wave's tiles; rocket_ppo.inc). The kernel writes them past the partial-gradient vectors, the
+workspace's last section, so this tool enlarges PPOGrad's workspace by that much.
 
     RR_LIB_PATH=tools/ab/lib_stamps.so python tools/ppo_stamps.py [--n 65536] --out F
 """
@@ -47,7 +47,7 @@ def main():
     nwg = min(128, max(1, ((bs + 31) // 32 + WAVES - 1) // WAVES))
     pf = 6412
     pack = (g._nbytes - 2 * KADVPART * 8) // 4 // 2 - nwg * pf
-    base = 2 * KADVPART * 2 + 2 * nwg * pf + 2 * pack  # floats: adv partials (doubles) | parts | packs
+    base = 2 * KADVPART * 2 + 2 * pack + 2 * nwg * pf  # floats: adv partials (doubles) | packs | parts
     extra = 2 * nwg * WAVES * 16
     g.ws = torch.zeros(base + extra + 64, dtype=torch.float32, device=dev)
     g._nbytes = g.ws.numel() * 4
