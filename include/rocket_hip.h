@@ -443,6 +443,25 @@ typedef struct rr_eval_trace {
 int rr_policy_evaluate_trace(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
                              const rr_eval_out* out, const rr_eval_trace* trace, float* obs, void* stream);
 
+/* ---- Evaluation under the exact integrator in ONE launch (ABI 14, added without a version bump: a
+ * new symbol, nothing existing changes) ----
+ * rr_policy_evaluate for RR_INT_DOPRI5 handles: the landing-success and final-error figures of the
+ * reference's EvalCallback, computed by the reference's own integrator (scipy RK45 with the brentq
+ * ground event, fp64, per env). A step is rr_policy_act's mean action followed by rr_step's exact
+ * step: obs = float32(state64 / normalizer) (6DOF; 3DOF: of the float32 state, as rr_step writes it),
+ * the pi tower and action heads, clip(mean, -1, 1), the adaptive solve, reward, TimeLimit and
+ * auto-reset; the fp64 state, v0, counter word and running return stay in registers between steps.
+ * Bitwise the episodes rr_policy_act + rr_step run where exp(log_std) * noise is absorbed by the
+ * mean (tests/test_gpu_eval_exact.py), whichever kernel variant rr_step picks for the handle's N.
+ * Rows, max_steps, obs, the untouched done list, asynchrony and capture are rr_policy_evaluate's;
+ * flags: RR_EVAL_EVENT / RR_EVAL_NONFINITE are solve_ivp's status 1 / -1. The running return is the
+ * handle's (rr_step keeps it whatever RR_FLAG_EPISODE_STATS says); the call leaves state64, the
+ * float32 state planes, v0, the counter words and the running returns as that many rr_step calls.
+ * RR_EINVAL: as rr_policy_evaluate, except that the handle must be an RR_INT_DOPRI5 one (RK4 / Euler
+ * handles go to rr_policy_evaluate). */
+int rr_policy_evaluate_exact(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
+                             const rr_eval_out* out, float* obs /* [n][state_dim] or NULL */, void* stream);
+
 /* RolloutBuffer.compute_returns_and_advantage: rewards / values / starts [T][n] (starts[t]
  * = episode-start flag of step t), last_value / last_done [n] -> advantages, returns [T][n].
  * The backward scan runs in fp64 (gamma, lam doubles since ABI 13) and each stored value is

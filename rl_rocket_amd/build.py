@@ -26,6 +26,12 @@ COLLECT_FLAGS = ["-mllvm", "-amdgpu-mfma-vgpr-form"]
 # a directory of its own: csrc/ itself holds the three translation units above and what they include
 # (tests/test_build_sources.py)
 SRC_EVAL_TRACE = os.path.join(HERE, "csrc", "eval_trace", "rocket_eval_trace.hip")
+# the one-launch exact-mode evaluation (rr_policy_evaluate_exact): the collect's policy towers around
+# the exact solver, in a module of its own for the same reason, with both units' settings. No
+# instantiation uses scratch with or without either (--resource-usage); the accumulators in VGPRs
+# take 2 (6DOF) to 38 (3DOF) AGPRs less, the scheduler setting changes no register figure here
+SRC_EVAL_EXACT = os.path.join(HERE, "csrc", "eval_exact", "rocket_eval_exact.hip")
+EVAL_EXACT_FLAGS = EXACT_FLAGS + COLLECT_FLAGS
 HEADER = os.path.join(ROOT, "include", "rocket_hip.h")
 OUT = os.path.join(HERE, "librocket_hip.so")
 # benchmark-only helper (not part of the product ABI): bench.py's event-timed direct-launch region
@@ -61,12 +67,12 @@ def command(resource_usage=False, out=OUT, defines=(), extra=(), src=SRC, compil
 
 
 def sources():
-    """Every file the translation units are compiled from: all of csrc/, the recording evaluation's
-    translation unit (which includes only files of csrc/) and the C-ABI header, sorted
-    (tests/test_build_sources.py checks that the #include graph stays inside this list)."""
+    """Every file the translation units are compiled from: all of csrc/, the recording and the
+    exact-mode evaluation's translation units (which include only files of csrc/) and the C-ABI
+    header, sorted (tests/test_build_sources.py checks that the #include graph stays inside this list)."""
     csrc = os.path.join(HERE, "csrc")
     return sorted([os.path.join(csrc, f) for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))]
-                  + [SRC_EVAL_TRACE, HEADER])
+                  + [SRC_EVAL_TRACE, SRC_EVAL_EXACT, HEADER])
 
 
 def source_hash():
@@ -85,10 +91,11 @@ def source_hash():
 
 
 def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
-    """The five steps of the library build: the main, exact-mode, collect and recording-evaluation
-    translation units compiled to objects (the latter three with EXACT_FLAGS / COLLECT_FLAGS /
-    COLLECT_FLAGS), then linked into `out`."""
+    """The six steps of the library build: the main, exact-mode, collect, recording-evaluation and
+    exact-evaluation translation units compiled to objects (the latter four with EXACT_FLAGS /
+    COLLECT_FLAGS / COLLECT_FLAGS / EVAL_EXACT_FLAGS), then linked into `out`."""
     o_main, o_exact, o_coll, o_trace = out + ".main.o", out + ".exact.o", out + ".collect.o", out + ".evaltrace.o"
+    o_evx = out + ".evalexact.o"
     c1 = command(resource_usage, o_main, defines, extra, SRC, compile_only=True, preload=preload)
     c2 = command(resource_usage, o_exact, defines, list(extra) + EXACT_FLAGS, SRC_EXACT, compile_only=True,
                  preload=preload)
@@ -96,12 +103,14 @@ def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
                  preload=preload)
     c4 = command(resource_usage, o_trace, defines, list(extra) + COLLECT_FLAGS, SRC_EVAL_TRACE, compile_only=True,
                  preload=preload)
-    c5 = [hipcc(), "--offload-arch=%s" % ARCH, "-shared", "-fPIC", "-o", out, o_main, o_exact, o_coll, o_trace]
-    return [c1, c2, c3, c4, c5]
+    c5 = command(resource_usage, o_evx, defines, list(extra) + EVAL_EXACT_FLAGS, SRC_EVAL_EXACT, compile_only=True,
+                 preload=preload)
+    c6 = [hipcc(), "--offload-arch=%s" % ARCH, "-shared", "-fPIC", "-o", out, o_main, o_exact, o_coll, o_trace, o_evx]
+    return [c1, c2, c3, c4, c5, c6]
 
 
 def build_lib(out=OUT, defines=(), extra=(), resource_usage=False, verbose=True, preload=4):
-    """Compile the four translation units (in parallel) and link `out`."""
+    """Compile the five translation units (in parallel) and link `out`."""
     cmds = commands(resource_usage, out, defines, extra, preload=preload)
     if verbose:
         for c in cmds:

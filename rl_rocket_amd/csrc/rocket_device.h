@@ -1,6 +1,6 @@
-// rocket_device.h — the device code shared by the four translation units of librocket_hip.so
-// (rocket_hip.hip, rocket_exact.hip, rocket_collect.hip, eval_trace/rocket_eval_trace.hip): the
-// constants and the host-derived
+// rocket_device.h — the device code shared by the five translation units of librocket_hip.so
+// (rocket_hip.hip, rocket_exact.hip, rocket_collect.hip, eval_trace/rocket_eval_trace.hip,
+// eval_exact/rocket_eval_exact.hip): the constants and the host-derived
 // parameter blocks (KParams, XParams), the buffer / intrinsic wrappers, the reset stream, the
 // RHS, integrators and ground event, reward and bounds, the obs tile store and the per-env
 // loads / stores that every step kernel inlines (physics_step, store_terminal, store_outputs).
@@ -8,8 +8,8 @@
 // the anonymous namespace: including it emits no kernel. At its end, host side: the variant
 // dispatcher (dispatch_env / dispatch_env_prec: every launch site calls a generic lambda with
 // compile-time tags for the handle's model, integrator and precision), the launch records
-// (EnvLaunch, ExactLaunch) and the one declaration of each hidden entry point through which the main
-// translation unit hands such a record to the other three.
+// (EnvLaunch, ExactLaunch, EvalExactLaunch) and the one declaration of each hidden entry point through
+// which the main translation unit hands such a record to the other four.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -1162,6 +1162,16 @@ struct ExactLaunch {
     double* state64;
     void* stream;
 };
+// ... and one whole exact-mode evaluation (rrx_launch_eval_exact)
+struct EvalExactLaunch {
+    int model, prec;         // eval_exact_kernel<MODEL, PREC>
+    unsigned grid;           // workgroups of rol::kEnvsPerBlock envs
+    const void* xp;          // XParams on the device
+    const void* bufs;        // the caller's Bufs
+    double* state64;
+    void* stream;
+};
+static_assert(std::is_trivially_copyable_v<EvalExactLaunch>, "EvalExactLaunch crosses TUs by memcpy");
 static_assert(std::is_trivially_copyable_v<EnvLaunch>, "EnvLaunch crosses TUs by memcpy");
 static_assert(std::is_trivially_copyable_v<ExactLaunch>, "ExactLaunch crosses TUs by memcpy");
 
@@ -1178,12 +1188,14 @@ inline T from_unit(const void* p)
 
 // The hidden entry points (not part of the C-ABI) through which the main translation unit launches
 // the kernels compiled in the others. Defined in rocket_exact.hip / rocket_collect.hip /
-// eval_trace/rocket_eval_trace.hip (rrc_launch_eval_trace); the
+// eval_trace/rocket_eval_trace.hip (rrc_launch_eval_trace) / eval_exact/rocket_eval_exact.hip
+// (rrx_launch_eval_exact); the
 // main TU adds weak stand-ins, so that a library built from rocket_hip.hip alone still loads.
-// launch points to the caller's ExactLaunch / EnvLaunch / PpoLaunch, io to its StepIO / RolloutIO /
-// EvalIO, trace to its EvalTraceIO.
+// launch points to the caller's ExactLaunch / EnvLaunch / EvalExactLaunch / PpoLaunch, io to its
+// StepIO / RolloutIO / EvalIO, trace to its EvalTraceIO.
 extern "C" {
 __attribute__((visibility("hidden"))) int rrx_launch_exact(const void* launch, const void* io);
+__attribute__((visibility("hidden"))) int rrx_launch_eval_exact(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrc_launch_collect(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrc_launch_eval(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrc_launch_eval_trace(const void* launch, const void* io, const void* trace);

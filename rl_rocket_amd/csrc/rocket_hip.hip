@@ -354,11 +354,12 @@ __global__ __launch_bounds__(kBlock) void narrow_kernel(const double* src, float
 
 // defined by the exact / collect / recording translation units (declared hidden in rocket_device.h);
 // these weak stand-ins (a library built from this file alone, e.g. a tools/ A/B variant) make
-// RR_INT_DOPRI5 steps, rr_rollout_collect, rr_policy_evaluate(_trace) and the learner fail loudly
+// RR_INT_DOPRI5 steps, rr_rollout_collect, rr_policy_evaluate(_trace / _exact) and the learner fail loudly
 // instead of failing to load
 constexpr int kNoUnit = (int)hipErrorInvalidDeviceFunction;
 extern "C" {
 __attribute__((weak)) int rrx_launch_exact(const void*, const void*) { return kNoUnit; }
+__attribute__((weak)) int rrx_launch_eval_exact(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_collect(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval_trace(const void*, const void*, const void*) { return kNoUnit; }
@@ -1448,10 +1449,12 @@ int rr_rollout_collect(rr_env* e, const float* params, int precision, uint64_t s
 
 namespace {
 
-// rr_policy_evaluate (trace == nullptr) and rr_policy_evaluate_trace: the argument checks, the
+// rr_policy_evaluate (trace == nullptr), rr_policy_evaluate_trace and rr_policy_evaluate_exact (`exact`:
+// the handle must be an RR_INT_DOPRI5 one, where the other two refuse it): the argument checks, the
 // kernel's EvalIO and the launch. `who` prefixes every message.
 int evaluate(rr_env* e, const char* who, const float* params, int precision, int n_episodes, int64_t max_steps,
-             const rr_eval_out* out, bool traced, const rr_eval_trace* trace, float* obs, void* stream)
+             const rr_eval_out* out, bool traced, const rr_eval_trace* trace, float* obs, void* stream,
+             bool exact = false)
 {
     const std::string w = std::string(who) + ": ";
     if (!e) return fail(RR_EINVAL, w + "null handle");
@@ -1467,8 +1470,11 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
         if (trace->n_slots < 1 || trace->steps < 1)
             return fail(RR_EINVAL, w + "trace->n_slots and trace->steps must be at least 1");
     }
-    if (e->p.integrator == RR_INT_DOPRI5)
-        return fail(RR_EINVAL, w + "RR_INT_DOPRI5 envs are evaluated step by step (rr_step)");
+    if (exact && e->p.integrator != RR_INT_DOPRI5)
+        return fail(RR_EINVAL, w + "RK4 / Euler envs are evaluated by rr_policy_evaluate");
+    if (!exact && e->p.integrator == RR_INT_DOPRI5)
+        return fail(RR_EINVAL, w + "RR_INT_DOPRI5 envs are evaluated step by step (rr_step) or by "
+                                   "rr_policy_evaluate_exact");
     if (!(e->p.flags & RR_FLAG_AUTO_RESET))
         return fail(RR_EINVAL, w + "the handle needs RR_FLAG_AUTO_RESET (episodes follow one another)");
     if (n_episodes < 1) return fail(RR_EINVAL, w + "n_episodes must be at least 1");
@@ -1489,9 +1495,14 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
     io.obs_vec_ok = ((uintptr_t)obs & 15u) == 0;
     const Bufs b = bufs_of(e);
     const EnvLaunch L = env_launch(e, prec, &b, stream);  // an auto-reset handle: its mode has kModeCounter
-    // compiled in the collect translation unit (rocket_collect.hip), as the collect kernel they derive from
+    // the fast modes' kernels are compiled in the collect translation units (rocket_collect.hip,
+    // eval_trace/), as the collect kernel they derive from
     hipError_t err;
-    if (traced) {
+    if (exact) {
+        // eval_exact_kernel (eval_exact/rocket_eval_exact.hip): eval_kernel's grid, one variant for every N
+        const EvalExactLaunch X = {e->p.model, prec, L.grid, e->d_xp, &b, e->state64, stream};
+        err = (hipError_t)rrx_launch_eval_exact(&X, &io);
+    } else if (traced) {
         EvalTraceIO t = {};
         t.slot = trace->slot;
         t.state = trace->state;
@@ -1522,6 +1533,13 @@ int rr_policy_evaluate_trace(rr_env* e, const float* params, int precision, int 
 {
     return evaluate(e, "rr_policy_evaluate_trace", params, precision, n_episodes, max_steps, out, true, trace, obs,
                     stream);
+}
+
+int rr_policy_evaluate_exact(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
+                             const rr_eval_out* out, float* obs, void* stream)
+{
+    return evaluate(e, "rr_policy_evaluate_exact", params, precision, n_episodes, max_steps, out, false, nullptr, obs,
+                    stream, true);
 }
 
 int rr_gae(int64_t T, int64_t n, const float* rewards, const float* values, const float* starts,

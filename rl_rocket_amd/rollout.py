@@ -1051,8 +1051,12 @@ class PolicyEvaluator:
 
     ``fused=True`` (default for an ``MlpActorCritic`` with 64x64 towers on an RK4 / Euler env): ONE
     launch (``rr_policy_evaluate``: the collect kernel's step loop with only the pi tower, state in
-    registers, nothing stored per step), capturable in a graph. ``fused=False`` (any policy whose
-    ``policy(obs)[0]`` is the action mean, and ``integrator="dopri5"``): the same algorithm in
+    registers, nothing stored per step), capturable in a graph. On an ``integrator="dopri5"`` batch
+    ``fused=True`` must be asked for and is ``rr_policy_evaluate_exact``: the same loop around the exact
+    solver, one launch where the step-by-step path takes two exact steps and a dozen small launches
+    per iteration, bit for bit the episodes of ``rr_policy_act`` + ``rr_step`` (it does not record:
+    ``record=`` with it raises). ``fused=False`` (any policy whose
+    ``policy(obs)[0]`` is the action mean, and the default for ``integrator="dopri5"``): the same algorithm in
     PyTorch ops, one ``batch.step`` per iteration for ``max_steps`` iterations; the un-reset terminal
     state and the reward terms of each step come from a shadow batch without auto-reset stepped
     from the same state, and envs that have finished are put back after every step.
@@ -1089,11 +1093,15 @@ class PolicyEvaluator:
         if self.max_steps <= 0:
             raise ValueError("an env without a TimeLimit needs max_steps")
         dopri = int(p.integrator) == _lib.RR_INT_DOPRI5
-        if fused is None:
+        if fused is None:  # an exact-mode batch keeps the step-by-step path unless asked (fused=True)
             fused = fused_grad_supported(policy, ns, na) and not dopri
-        if fused and (dopri or not fused_grad_supported(policy, ns, na)):
-            raise ValueError("fused evaluation needs an MlpActorCritic with 64x64 towers and an RK4 / Euler env")
+        if fused and not fused_grad_supported(policy, ns, na):
+            raise ValueError("fused evaluation needs an MlpActorCritic with 64x64 towers")
+        if fused and dopri and record is not None:
+            raise ValueError("record= on an integrator=\"dopri5\" batch needs fused=False (the one-launch exact "
+                             "evaluation does not record)")
         self.fused = bool(fused)
+        self._exact = self.fused and dopri
         if policy_dtype not in POLICY_PRECISIONS:
             raise ValueError("policy_dtype must be one of %s" % sorted(POLICY_PRECISIONS))
         if policy_dtype != "fp32" and not self.fused:
@@ -1183,9 +1191,10 @@ class PolicyEvaluator:
                                                           ctypes.byref(self._trace_io), _ptr(env.obs), stream),
                        "rr_policy_evaluate_trace")
             return self.result
-        _lib.check(self._lib.rr_policy_evaluate(env._h, _ptr(self._pack.pack()), self._pack.prec, self.n_episodes,
-                                                self.max_steps, ctypes.byref(self._out), _ptr(env.obs), stream),
-                   "rr_policy_evaluate")
+        call, name = ((self._lib.rr_policy_evaluate_exact, "rr_policy_evaluate_exact") if self._exact else
+                      (self._lib.rr_policy_evaluate, "rr_policy_evaluate"))
+        _lib.check(call(env._h, _ptr(self._pack.pack()), self._pack.prec, self.n_episodes, self.max_steps,
+                        ctypes.byref(self._out), _ptr(env.obs), stream), name)
         return self.result
 
     # -- fused=False: the kernel's algorithm in PyTorch ops ---------------------------------------------------

@@ -13,6 +13,19 @@
           env-steps per second; `--reps` evaluations, each from a new reset.
   unfused the same evaluation through PolicyEvaluator(fused=False), once (it runs all 800
           iterations: it cannot leave early without a synchronise).
+
+    python tools/eval_bench.py --integrator dopri5 [--tl 800] [--reps 5] [--out profiles/eval_exact/eval_exact_bench.json]
+
+  the exact mode's evaluation (rr_policy_evaluate_exact) against the step-by-step path on the same
+  work: 6DOF, fp32 towers, the scaled test policy (tests/rollout_ref.py), one episode per env from a
+  fresh reset under TimeLimit `--tl`. Two batches with the same seed, one evaluated with
+  PolicyEvaluator(fused=True), one with fused=False (rollout.py's _run_unfused: `--tl` iterations of
+  a PyTorch policy forward, two exact steps and the state round trips), alternating, `--reps` timed
+  runs each after a warm-up run, HIP events around run(). The record holds every run, the medians
+  and spreads, env-steps per second, the ratio, and `--tl` x the committed rocprofv3 time of one
+  step_exact_kernel launch (profiles/r06/r06h/: 25.9 us) as the "launch overhead removed, slowest
+  wave of every step kept" yardstick. `fixed`: 64 steps of every env in one launch against 64 x
+  (rr_policy_act + rr_step), the same work bit for bit (exact_fixed_work).
 """
 import argparse
 import json
@@ -42,6 +55,8 @@ def main():
     ap.add_argument("--blocks", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-unfused", action="store_true")
+    ap.add_argument("--integrator", choices=("rk4", "dopri5"), default="rk4")
+    ap.add_argument("--tl", type=int, default=800, help="TimeLimit of the dopri5 leg")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -59,6 +74,17 @@ def main():
     pol = MlpActorCritic(14, 3).to(dev)
     rec = {"n": n, "model": "6DOF", "policy_dtype": "fp32", "max_episode_steps": 800,
            "device": torch.cuda.get_device_name(0), "source_hash": build.source_hash()}
+
+    def write(rec):
+        print(json.dumps(rec))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(rec, indent=1) + "\n")
+
+    if args.integrator == "dopri5":
+        write(exact_leg(args, rec, dev))
+        return
 
     def env():
         return RocketBatch(n, model=6, device=dev, max_episode_steps=800, **ENV_CONFIG_6DOF)
@@ -106,12 +132,126 @@ def main():
     rec["real"] = real(True, args.reps)
     if not args.no_unfused:
         rec["real_unfused"] = real(False, 1)
-    line = json.dumps(rec)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(json.dumps(rec, indent=1) + "\n")
+    write(rec)
+
+
+# rocprofv3 kernel time of one step_exact_kernel launch at N = 65 536, 6DOF (profiles/r06/r06h/)
+STEP_EXACT_US = 25.9
+
+
+def exact_leg(args, rec, dev):
+    """The --integrator dopri5 record (see the module docstring)."""
+    import torch
+    from rl_rocket_amd.batch import RocketBatch
+    from rl_rocket_amd.params import ENV_CONFIG_6DOF
+    from rl_rocket_amd.rollout import PolicyEvaluator
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from rollout_ref import scaled_policy
+
+    n, tl = args.n, args.tl
+    pol = scaled_policy(14, 3, seed=5, head_scale=1.0).to(dev)
+    rec.update(integrator="dopri5", max_episode_steps=tl, policy="tests/rollout_ref.scaled_policy(14, 3, seed=5, "
+               "head_scale=1.0)", n_episodes=1, reps=args.reps)
+    legs = {}
+    for name, fused in (("fused", True), ("unfused", False)):
+        b = RocketBatch(n, model=6, device=dev, max_episode_steps=tl, integrator="dopri5",
+                        **dict(ENV_CONFIG_6DOF, seed=1234))
+        legs[name] = (b, PolicyEvaluator(b, pol, n_episodes=1, fused=fused), [])
+    for r in range(args.reps + 1):  # run 0 is the warm-up; the two legs alternate, each from the same reset
+        for name, (b, e, runs) in legs.items():
+            b.reset()
+            torch.cuda.synchronize()
+            us = timed(e.run, 1)
+            ln = e.result.ep_length[0].long()
+            waves = torch.nn.functional.pad(ln, (0, (-n) % 64)).view(-1, 64).max(dim=1).values
+            s = e.result.stats()
+            if r:
+                runs.append({"us": us, "env_steps": int(ln.sum()), "wave_steps": int(waves.sum()),
+                             "wave_steps_max": int(waves.max()),
+                             "env_steps_per_s": float(ln.sum()) / (us * 1e-6), "mean_ep_length": s["mean_ep_length"],
+                             "mean_reward": s["mean_reward"], "landing_success": s["ep_statistic/landing_success"],
+                             "episodes": s["episodes"], "unfinished": s["unfinished"]})
+    for name, (b, e, runs) in legs.items():
+        us = [x["us"] for x in runs]
+        rec[name] = {"runs": runs, "us_median": statistics.median(us), "us_min": min(us), "us_max": max(us),
+                     "env_steps_per_s_median": statistics.median(x["env_steps_per_s"] for x in runs)}
+        b.close()
+    f, u = rec["fused"], rec["unfused"]
+    yard = tl * STEP_EXACT_US
+    # the longest wave of the one-launch call: the launches a step-by-step loop that could leave early would need
+    longest = statistics.median(x["wave_steps_max"] for x in f["runs"])
+    rec.update(longest_wave_steps_median=longest, yardstick_longest_wave_us=longest * STEP_EXACT_US,
+               fused_us_per_step_of_longest_wave=f["us_median"] / longest)
+    rec.update(ratio_unfused_over_fused=u["us_median"] / f["us_median"],
+               spreads_overlap=bool(f["us_max"] >= u["us_min"]),
+               yardstick_us=yard, yardstick="%d x %.1f us (one step_exact_kernel launch, profiles/r06/r06h/)"
+               % (tl, STEP_EXACT_US), yardstick_over_fused=yard / f["us_median"])
+    rec["fixed"] = exact_fixed_work(args, dev, pol)
+    return rec
+
+
+def exact_fixed_work(args, dev, pol, k=64):
+    """The same `k` steps of every env, once in one launch (n_episodes = max_steps = k: no env ends k
+    episodes in k steps, so every wave runs k iterations with all lanes stepping) and once as k times
+    rr_policy_act + rr_step, from the same reset, alternating. log_std = -60 makes rr_policy_act's
+    action the mean, and the stepped batch starts from the exact mode's obs rows, so both paths do the
+    same arithmetic: `same_state` records that they end in the same fp64 state bit for bit. What
+    differs is where the waves meet: never, or after every step."""
+    import copy
+    import ctypes
+
+    import numpy as np
+    import torch
+    from rl_rocket_amd import _lib
+    from rl_rocket_amd.batch import RocketBatch, _ptr
+    from rl_rocket_amd.params import ENV_CONFIG_6DOF
+    from rl_rocket_amd.rollout import PolicyEvaluator, PolicyPack
+
+    n = args.n
+    pol = copy.deepcopy(pol)
+    with torch.no_grad():
+        pol.log_std.fill_(-60.0)
+    bf, bs = [RocketBatch(n, model=6, device=dev, max_episode_steps=args.tl, integrator="dopri5",
+                          **dict(ENV_CONFIG_6DOF, seed=1234)) for _ in range(2)]
+    ev = PolicyEvaluator(bf, pol, n_episodes=k, max_steps=k, fused=True)
+    pack = PolicyPack(pol, 14, 3, dev)
+    lib = _lib.load()
+    f32 = dict(dtype=torch.float32, device=dev)
+    it = torch.zeros(1, dtype=torch.int64, device=dev)
+    act_env, act, val, lp = torch.zeros((n, 3), **f32), torch.zeros((n, 3), **f32), torch.zeros(n, **f32), torch.zeros(n, **f32)
+    norm = torch.tensor(np.asarray(bs.cfg.state_normalizer, dtype=np.float64), device=dev)
+
+    def stepwise():
+        params = pack.pack()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for t in range(k):
+            _lib.check(lib.rr_policy_act(_ptr(params), 14, 3, pack.prec, n, 0, _ptr(bs.obs), 11, _ptr(it), t,
+                                         _ptr(act_env), _ptr(act), _ptr(val), _ptr(lp), None, None, None, None, 0.0,
+                                         None, None, None, stream), "rr_policy_act")
+            bs.step(act_env)
+
+    one, many, same, ends = [], [], True, 0
+    for r in range(args.reps + 1):  # run 0 is the warm-up
+        bf.reset()
+        torch.cuda.synchronize()
+        t1 = timed(ev.run, 1)
+        bs.reset()
+        bs.obs.copy_((bs.get_state64()[0] / norm[:, None]).float().T)
+        torch.cuda.synchronize()
+        tk = timed(stepwise, 1)
+        same = same and torch.equal(bf.get_state64()[0], bs.get_state64()[0])
+        ends = int(ev.result.episodes.sum())
+        if r:
+            one.append(t1)
+            many.append(tk)
+    bf.close()
+    bs.close()
+    m1, mk = statistics.median(one), statistics.median(many)
+    return {"steps": k, "one_launch_us": one, "stepwise_us": many, "one_launch_us_median": m1, "stepwise_us_median": mk,
+            "one_launch_us_per_step": m1 / k, "stepwise_us_per_step": mk / k, "step_exact_kernel_us": STEP_EXACT_US,
+            "same_state": bool(same), "episode_ends_in_the_last_run": ends,
+            "stepwise": "k x (rr_policy_act + rr_step), direct launches from Python, HIP events around the loop"}
 
 
 if __name__ == "__main__":
