@@ -36,7 +36,10 @@ constexpr int kStAux = 0;
 // where the whole batch's state is a few MB, so the end-of-kernel release has no dirty state
 // lines to write back. A/B at N = 65536: direct launches 4.13-4.26 vs 4.34-4.55 us per step,
 // hipGraph replays K = 20 4.39-4.41 vs 4.47-4.48, K = 2000 equal; at N = 524288 (plain kernel,
-// default policy kept) it had cost 10-25 %.
+// default policy kept) it had cost 10-25 %. Round 8: the done path's stores of
+// these kernels too (terminal rows, terminal return / length, the wave's done word), the last ones
+// that left dirty lines: 4.62 -> 4.39 us per launch in steady state, 4.16 -> 4.05 fresh
+// (DESIGN.md §3 'Round 8').
 constexpr int kStAuxHelp = 16;
 // caller-owned outputs (obs, reward, done, truncated): sc1 = device-scope write-through, the
 // outputs leave L2 while the kernel runs instead of in the end-of-kernel writeback (A/B at

@@ -84,6 +84,7 @@ __global__ __launch_bounds__(HELP ? 2 * WPB * kWave : WPB * kWave) __attribute__
     const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const uint32_t n = n_envs;
     RR_STAMPS_BEGIN(4);  // diagnostic builds only (rocket_stamps.h)
+    RR_SUB_BEGIN(3);     // the done tail, in cycles after stamp 2: terminal rows issued, flag seen, candidate landed
     if constexpr (HELP) {
         if (wv >= (uint32_t)WPB) {
             // the helper role reads its parameters through the device copy (B.kp): kernel-argument
@@ -186,12 +187,19 @@ __global__ __launch_bounds__(HELP ? 2 * WPB * kWave : WPB * kWave) __attribute__
     // side expands the masks into the sorted index list, rr_fetch_done).
     const bool dv = done && valid;
     const uint64_t m = __ballot(dv);
-    if (lane == 0) B.done_bits[wave_idx] = m;
+    if (lane == 0) {
+        // HELP: write-through like every other store of these kernels (kStAuxHelp): a 128-B line of
+        // done words is written by waves of four XCDs, and left dirty in their L2s it is what the
+        // end-of-kernel release has to find and write back even when no env is done
+        if constexpr (HELP) __hip_atomic_store(&B.done_bits[wave_idx], m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else B.done_bits[wave_idx] = m;
+    }
     if (m) {
         // plain kernels past the MALL: the 4-B terminal return / length and the reset v0 leave as
         // whole lines, from every lane of a wave with a done lane (the others' values are not
         // read: terminal rows count at done indices only; their v0 is unchanged)
-        if (dv) store_terminal<NS, HELP ? 0 : kTermAuxLarge, HELP>(B, i, vo, plane, o, ret, el);
+        if (dv) store_terminal<NS, HELP ? kStAuxHelp : kTermAuxLarge, HELP>(B, i, vo, plane, o, ret, el);
+        RR_SUB_STAMP(0, 2);
         if constexpr (!HELP) {
             if ((mode & kModeWholeLines) ? valid : dv) {
                 bst_f<0>(make_rsrc(B.term_ret, plane), ret, vo, 0);
@@ -202,10 +210,12 @@ __global__ __launch_bounds__(HELP ? 2 * WPB * kWave : WPB * kWave) __attribute__
             if constexpr (HELP) {
                 while (__hip_atomic_load(&cflag[wv], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u)
                     __builtin_amdgcn_s_sleep(1);
+                RR_SUB_STAMP(1, 2);
                 const float* row = &cand[wv][lane * kCandRow];
 #pragma unroll
                 for (int j = 0; j < NS; ++j) y1[j] = row[j];
                 v0 = row[NS];
+                RR_SUB_STAMP_AFTER(2, 2, y1, NS);
             } else {
 #pragma unroll
                 for (int j = 0; j < NS; ++j) y1[j] = ic_s[j];
@@ -248,9 +258,11 @@ __global__ __launch_bounds__(HELP ? 2 * WPB * kWave : WPB * kWave) __attribute__
                                   io.obs_vec_ok);
     }
     // lanes 0..2: barrier / loads / compute cycles; 3: the tail (outputs issued); 4, 5: the wave's
-    // s_memrealtime start / end (100 MHz, low 32 bits, bit patterns in the float slots)
+    // s_memrealtime start / end (100 MHz, low 32 bits, bit patterns in the float slots); 6-8: the
+    // done tail's sub-stamps (tools/step_stamps_steady.py)
     RR_STAMP(3);
     RR_STAMPS_WRITE(io.reward, i, lane, valid, true);
+    RR_SUB_WRITE(io.reward, i, lane, valid, 6);
 }
 
 template <int MODEL>

@@ -10,6 +10,10 @@
 // values overwrite dst[i] (a per-env output such as the reward) of the wave's first lanes.
 // step_kernel's phase 0 reads "entry -> past the helper barrier, loads in flight": the helper-wave
 // kernels issue every load ahead of the barrier, so phase 1 (-> state landed) starts inside the round trip.
+// Sub-stamps (step_kernel's done tail): RR_SUB_BEGIN(N), RR_SUB_STAMP(k, ref) records the cycles since
+// phase stamp `ref` at a point only some waves (or only some lanes of a wave) reach, RR_SUB_WRITE(dst, i,
+// lane, ok, first) writes sub-stamp k of the wave (0 where no lane reached it; a reached one is odd) to
+// dst[i] of lane first + k.
 // Accumulated stamps (the collect's step loop): RR_ACC_BEGIN(N), RR_ST(p) adds the cycles since
 // the previous stamp to phase p, RR_ACC_WRITE(dst, base, lane, ok) writes phase `lane` to dst[base + lane].
 #pragma once
@@ -46,6 +50,32 @@
         }                                                                     \
         if ((lane) < (uint32_t)rr_st_n + ((rt) ? 2u : 0u) && (ok)) (dst)[i] = rr_v;      \
     } while (0)
+#define RR_SUB_BEGIN(N)                                                       \
+    constexpr int rr_sub_n = (N);                                             \
+    uint32_t rr_sub_c[rr_sub_n] = {}
+#define RR_SUB_STAMP(k, ref)                                                  \
+    do {                                                                      \
+        __builtin_amdgcn_sched_barrier(0);                                    \
+        rr_sub_c[k] = ((uint32_t)__builtin_amdgcn_s_memtime() - rr_st_c[ref]) | 1u; \
+        __builtin_amdgcn_sched_barrier(0);                                    \
+    } while (0)
+#define RR_SUB_STAMP_AFTER(k, ref, arr, NV)                                   \
+    do {                                                                      \
+        _Pragma("unroll") for (int rr_j = 0; rr_j < (NV); ++rr_j)             \
+            asm volatile("" ::"v"((arr)[rr_j]));                              \
+        RR_SUB_STAMP(k, ref);                                                 \
+    } while (0)
+#define RR_SUB_WRITE(dst, i, lane, ok, first)                                 \
+    do {                                                                      \
+        float rr_sv = 0.0f;                                                   \
+        _Pragma("unroll") for (int rr_k = 0; rr_k < rr_sub_n; ++rr_k) {       \
+            const uint64_t rr_b = __ballot(rr_sub_c[rr_k] != 0u);             \
+            const uint32_t rr_u = rr_b ? (uint32_t)__builtin_amdgcn_readlane( \
+                (int)rr_sub_c[rr_k], (int)__builtin_ctzll(rr_b)) : 0u;        \
+            rr_sv = (lane) == (uint32_t)((first) + rr_k) ? (float)rr_u : rr_sv; \
+        }                                                                     \
+        if ((lane) >= (uint32_t)(first) && (lane) < (uint32_t)((first) + rr_sub_n) && (ok)) (dst)[i] = rr_sv; \
+    } while (0)
 #define RR_ACC_BEGIN(N)                                                       \
     constexpr int rr_acc_n = (N);                                             \
     uint32_t rr_acc[rr_acc_n] = {};                                           \
@@ -74,6 +104,16 @@
     do {                           \
     } while (0)
 #define RR_STAMPS_WRITE(dst, i, lane, ok, rt) \
+    do {                                      \
+    } while (0)
+#define RR_SUB_BEGIN(N) static_assert((N) > 0, "")
+#define RR_SUB_STAMP(k, ref) \
+    do {                     \
+    } while (0)
+#define RR_SUB_STAMP_AFTER(k, ref, arr, NV) \
+    do {                                    \
+    } while (0)
+#define RR_SUB_WRITE(dst, i, lane, ok, first) \
     do {                                      \
     } while (0)
 #define RR_ACC_BEGIN(N) static_assert((N) > 0, "")
