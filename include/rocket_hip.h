@@ -313,7 +313,21 @@ int rr_policy_pack(int obs_dim, int act_dim, int precision, const float* const* 
  *   If reward_out != NULL: reward_out[i] = prev_reward[i] + gamma * V(prev_term_obs[i])
  *   where prev_truncated[i] (the timeout bootstrap of step t-1; rr_step's outputs and
  *   rr_get_buffers' terminal_obs). If start_out != NULL: start_out[i] = done[i] (episode
- *   start flags of step t). */
+ *   start flags of step t).
+ *   Input domain and accuracy (every rr_policy_* / rr_rollout_* call; pinned at these edges by
+ *   tests/test_gpu_policy_edges.py against float64): any obs is accepted. RR_POLICY_FP32 and
+ *   RR_POLICY_BF16 hand a NaN component on to the row's value, mean and log_prob. RR_POLICY_FP16X3
+ *   converts obs * 2^8 to fp16 and saturates it at fp16's largest finite value: a component past
+ *   |obs| = 255.875 (65504 / 2^8) is read as +-255.875, so every finite obs gives finite outputs
+ *   (before this saturation such a row's outputs were all NaN). The saturating instruction returns
+ *   its smallest operand for a NaN, so on this path a NaN component is read as -255.875 and +-inf as
+ *   +-255.875: rows with non-finite obs give finite outputs there and must be recognised by the
+ *   caller (rr_step ends such an env's episode on its own state check). The worst-case error of
+ *   value and mean grows linearly with |obs| (the layer-1 term (obs_dim + 2) u |W1| |obs|, u = 2^-24
+ *   for fp32 and 2^-21 for fp16x3); measured against float64 on an SB3-initialised policy perturbed by
+ *   0.3 N(0, 1): 1.3e-6 (value) / 1.5e-6 (mean) at obs ~ N(0, 1) and 5.3e-6 / 9.9e-6 at obs uniform
+ *   in +-90 (the envs' own worst case) for fp16x3, 2.7e-6 / 4.8e-6 and 3.2e-6 / 8.0e-6 for fp32; with
+ *   the tower weights 8 times larger 1.2e-4 / 1.4e-4 (fp16x3) and 3.5e-5 / 1.5e-4 (fp32) at +-90. */
 int rr_policy_act(const float* params, int obs_dim, int act_dim, int precision, int64_t n, int64_t env_id_offset,
                   const float* obs, uint64_t seed, const uint64_t* iter, int t, float* action_env, float* action,
                   float* value, float* log_prob, float* obs_copy, const float* prev_term_obs,

@@ -95,6 +95,16 @@ template <> struct XOp<2> { using T = F16Pair; };
 
 constexpr float kF16In = 256.0f;            // operand scale of the split-fp16 path (2^8)
 constexpr float kF16Out = 1.0f / 65536.0f;  // accumulator scale back (2^-16)
+constexpr float kF16Max = 65504.0f;         // largest finite fp16
+
+// An obs component at the operand scale, saturated into fp16's finite range: past |obs| = 255.875
+// (65504 / 2^8) the conversion of split_f16 gives hi = +-inf, lo = -+inf and every hidden unit
+// inf - inf. The row is then evaluated at the obs clamped to +-255.875 (hi = +-65504, lo = 0: both
+// halves come from the clamped value). One v_med3_f32, which returns min3 of its operands when one
+// is NaN: a NaN component reads as -255.875 and +-inf as +-255.875 (every input gives finite
+// outputs on this path; the fp32 and bf16 paths hand a NaN on). Values inside the range keep their
+// bits.
+__device__ __forceinline__ float f16_operand(float x) { return __builtin_amdgcn_fmed3f(kF16In * x, -kF16Max, kF16Max); }
 
 // v = hi + lo (fp16 halves of v, element-wise; v already scaled). Both halves are converted with
 // packed RNE conversions; lo = v - float(hi) has one rounding whichever instruction forms it.
@@ -543,7 +553,7 @@ __device__ __forceinline__ void load_x(const float* so, int lane,
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int k = 16 * s + 8 * half + j;
-                    v[j] = k < OBS ? kF16In * so[(32 * n + r) * OBS + k] : 0.0f;
+                    v[j] = k < OBS ? f16_operand(so[(32 * n + r) * OBS + k]) : 0.0f;
                 }
                 split_f16(v, x[n][s]);
             } else {

@@ -207,8 +207,8 @@ __device__ __forceinline__ void regs_x(const float* o, typename pol::XOp<PREC>::
             if constexpr (PREC == 2) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    v0[j] *= pol::kF16In;
-                    v1[j] *= pol::kF16In;
+                    v0[j] = pol::f16_operand(v0[j]);  // saturated as in pol::load_x
+                    v1[j] = pol::f16_operand(v1[j]);
                 }
                 pol::split_f16(v0, x[0][s]);
                 pol::split_f16(v1, x[1][s]);

@@ -273,7 +273,9 @@ class DeviceRollout:
     + bootstrap + GAE launches. All three paths produce bitwise the same rollout.
     ``policy_dtype="fp16x3"`` (fused only) runs the towers on fp16 MFMA with every operand
     split into fp16 hi + lo halves and three MFMAs per k step: fp32-level results (values
-    within ~3e-6 of the PyTorch fp32 policy, as the fp32 path) at 1.44x the collection rate.
+    within ~3e-6 of the PyTorch fp32 policy at obs of O(1), as the fp32 path; ~1e-5 at the envs'
+    largest obs of +-90; obs components past +-255.875, the fp16 operand range, are read as
+    +-255.875: INTEGRATION.md) at 1.44x the collection rate.
     ``policy_dtype="bf16"`` (fused only, opt-in) runs the towers on bf16 MFMA with fp32
     accumulation: actions / values / log-probs then differ from the fp32 policy by the bf16
     rounding of obs, weights and the first hidden layer (the stored log-probs are those of
