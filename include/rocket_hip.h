@@ -376,6 +376,71 @@ int rr_rollout_collect(rr_env* e, const float* params, int precision, uint64_t s
                        float* last_start, float* obs, float* reward, uint8_t* done, uint8_t* truncated, float* terms,
                        void* stream);
 
+/* ---- Training-time episode statistics from the collect (ABI 14, added without a version bump: two
+ * new symbols and a new struct, nothing existing changes) ----
+ * Replaces what SB3 logs from Monitor-wrapped envs every iteration (reference main_6DOF.py:18-24,
+ * 62-69: rollout/ep_rew_mean, rollout/ep_len_mean, train/explained_variance).
+ * rr_rollout_collect_stats IS rr_rollout_collect (same arguments, same arithmetic in the same order:
+ * the rollout buffers, the env outputs and the handle's state are left bit for bit the same) and, in
+ * the same launch, accounts for every episode an env finishes in it, whichever step it ends on and
+ * however many one env finishes, and for the rollout's samples after the GAE scan. A second launch
+ * on the same stream folds the per-wave rows (`partials`) into `out`, 16 slots of 8 bytes:
+ *   EPISODES .. NONFINITE  int64: episodes finished, the sum of their lengths (the TimeLimit's
+ *                          elapsed count, as rr_copy_terminal's ep_len), and how many landed (the
+ *                          rule of RR_EVAL_LANDED), ended on the ground event, by a bounds violation,
+ *                          by the TimeLimit, on a non-finite state (an episode can set several)
+ *   RET_SUM, RET_SQ        fp64: sum of the episodes' returns (the fp32 running return of
+ *                          rr_copy_terminal's ep_return, widened) and of their squares
+ *   RET_MIN, RET_MAX       fp64: their extremes, +inf / -inf without an episode. fmin / fmax: a NaN
+ *                          return (a non-finite episode) is skipped here and makes the two sums NaN
+ *   Y_SUM .. D_SQ          fp64 over the n_steps * n samples: sums of y, y^2, d, d^2 with
+ *                          y = buf_return[t][i], d = y - buf_value[t][i] (SB3 explained_variance =
+ *                          1 - Var(d) / Var(y))
+ *   SAMPLES                int64: n_steps * n
+ * Every fold runs in a fixed order (lanes, then waves): no atomics, the same bits on every run.
+ * When `accum` is given the call also folds `out` into it (sums add, min / max fold) and never
+ * zeroes it: the caller starts a window with zeros and +inf / -inf in RET_MIN / RET_MAX.
+ * RR_EINVAL: everything rr_rollout_collect refuses; stats, partials or out NULL; partials not
+ * 128-B aligned, out or accum not 8-B aligned; buf_advantage NULL (Y_SUM .. SAMPLES need the scan);
+ * a handle without RR_FLAG_EPISODE_STATS (the running return is then not carried across launches: an
+ * episode spanning two collects would report a short return) or without RR_FLAG_AUTO_RESET.
+ * Two launches, asynchronous on `stream`, capturable in a hipGraph, no allocation. */
+enum {
+    RR_RSTAT_EPISODES = 0,  /* int64 */
+    RR_RSTAT_LEN_SUM,       /* int64 */
+    RR_RSTAT_LANDED,        /* int64 */
+    RR_RSTAT_END_EVENT,     /* int64 */
+    RR_RSTAT_END_BOUNDS,    /* int64 */
+    RR_RSTAT_END_TRUNCATED, /* int64 */
+    RR_RSTAT_END_NONFINITE, /* int64 */
+    RR_RSTAT_RET_SUM,       /* fp64 */
+    RR_RSTAT_RET_SQ,        /* fp64 */
+    RR_RSTAT_RET_MIN,       /* fp64 */
+    RR_RSTAT_RET_MAX,       /* fp64 */
+    RR_RSTAT_Y_SUM,         /* fp64 */
+    RR_RSTAT_Y_SQ,          /* fp64 */
+    RR_RSTAT_D_SUM,         /* fp64 */
+    RR_RSTAT_D_SQ,          /* fp64 */
+    RR_RSTAT_SAMPLES,       /* int64 */
+    RR_RSTAT_SLOTS          /* 16: a block is 128 bytes */
+};
+
+typedef struct rr_rollout_stats {
+    void* partials;   /* device, 128-B aligned, rr_rollout_stats_rows(n) * 128 bytes of scratch */
+    void* out;        /* device [16] x 8 bytes: this collect's totals, RR_RSTAT_* slots */
+    void* accum;      /* device [16] x 8 bytes or NULL: running totals, folded into, never zeroed by the call */
+} rr_rollout_stats;
+
+/* rows of `partials` for n envs: one per 64 envs, rounded up (<= 0 for n <= 0) */
+int64_t rr_rollout_stats_rows(int64_t n);
+
+int rr_rollout_collect_stats(rr_env* e, const float* params, int precision, uint64_t seed, const uint64_t* iter,
+                             int n_steps, double gamma, double gae_lambda, float* buf_obs, float* buf_action,
+                             float* buf_value, float* buf_log_prob, float* buf_start, float* buf_reward,
+                             float* buf_advantage, float* buf_return, float* last_value, float* last_done,
+                             float* last_start, float* obs, float* reward, uint8_t* done, uint8_t* truncated,
+                             float* terms, const rr_rollout_stats* stats, void* stream);
+
 /* ---- On-device deterministic policy evaluation (ABI 14) ----
  * Replaces stable_baselines3 EvalCallback / evaluate_policy(deterministic=True) on an
  * EpisodeAnalyzer-wrapped env (reference main_6DOF.py:60-103: EvalCallback(eval_env, n_eval_episodes=5,

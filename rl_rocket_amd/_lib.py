@@ -94,6 +94,23 @@ class RrEvalOut(ctypes.Structure):
     ]
 
 
+class RrRolloutStats(ctypes.Structure):
+    """Mirror of ``rr_rollout_stats`` (device pointers; ``accum`` may be NULL)."""
+
+    _fields_ = [
+        ("partials", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("accum", ctypes.c_void_p),
+    ]
+
+
+# the slots of a statistics block (rocket_hip.h RR_RSTAT_*): 16 x 8 bytes
+(RR_RSTAT_EPISODES, RR_RSTAT_LEN_SUM, RR_RSTAT_LANDED, RR_RSTAT_END_EVENT, RR_RSTAT_END_BOUNDS, RR_RSTAT_END_TRUNCATED,
+ RR_RSTAT_END_NONFINITE, RR_RSTAT_RET_SUM, RR_RSTAT_RET_SQ, RR_RSTAT_RET_MIN, RR_RSTAT_RET_MAX, RR_RSTAT_Y_SUM,
+ RR_RSTAT_Y_SQ, RR_RSTAT_D_SUM, RR_RSTAT_D_SQ, RR_RSTAT_SAMPLES, RR_RSTAT_SLOTS) = range(17)
+RR_RSTAT_INT_SLOTS = (0, 1, 2, 3, 4, 5, 6, 15)
+
+
 class RrEvalTrace(ctypes.Structure):
     """Mirror of ``rr_eval_trace`` (device pointers; ``action`` / ``terms`` may be NULL)."""
 
@@ -148,6 +165,10 @@ SIGNATURES = {
                                        _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rr_rollout_collect": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_uint64, _P, ctypes.c_int, ctypes.c_double,
                                           ctypes.c_double] + [_P] * 17),
+    "rr_rollout_stats_rows": (ctypes.c_int64, [ctypes.c_int64]),
+    "rr_rollout_collect_stats": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_uint64, _P, ctypes.c_int,
+                                                ctypes.c_double, ctypes.c_double] + [_P] * 16 +
+                                 [ctypes.POINTER(RrRolloutStats), _P]),
     "rr_policy_evaluate": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                           ctypes.POINTER(RrEvalOut), _P, _P]),
     "rr_policy_evaluate_trace": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int64,

@@ -32,6 +32,10 @@ SRC_EVAL_TRACE = os.path.join(HERE, "csrc", "eval_trace", "rocket_eval_trace.hip
 # take 2 (6DOF) to 38 (3DOF) AGPRs less, the scheduler setting changes no register figure here
 SRC_EVAL_EXACT = os.path.join(HERE, "csrc", "eval_exact", "rocket_eval_exact.hip")
 EVAL_EXACT_FLAGS = EXACT_FLAGS + COLLECT_FLAGS
+# the collect that also accounts for the episodes it finishes (rr_rollout_collect_stats): the collect
+# TU's settings in a module of its own, again so that the existing kernels keep their machine code
+SRC_COLLECT_STATS = os.path.join(HERE, "csrc", "collect_stats", "rocket_collect_stats.hip")
+INC_COLLECT_STATS = os.path.join(HERE, "csrc", "collect_stats", "rocket_collect_stats.inc")
 HEADER = os.path.join(ROOT, "include", "rocket_hip.h")
 OUT = os.path.join(HERE, "librocket_hip.so")
 # benchmark-only helper (not part of the product ABI): bench.py's event-timed direct-launch region
@@ -68,11 +72,11 @@ def command(resource_usage=False, out=OUT, defines=(), extra=(), src=SRC, compil
 
 def sources():
     """Every file the translation units are compiled from: all of csrc/, the recording and the
-    exact-mode evaluation's translation units (which include only files of csrc/) and the C-ABI
-    header, sorted (tests/test_build_sources.py checks that the #include graph stays inside this list)."""
+    exact-mode evaluation's translation units (which include only files of csrc/), the statistics
+    collect's unit with the .inc beside it and the C-ABI header, sorted (tests/test_build_sources.py checks that the #include graph stays inside this list)."""
     csrc = os.path.join(HERE, "csrc")
     return sorted([os.path.join(csrc, f) for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))]
-                  + [SRC_EVAL_TRACE, SRC_EVAL_EXACT, HEADER])
+                  + [SRC_EVAL_TRACE, SRC_EVAL_EXACT, SRC_COLLECT_STATS, INC_COLLECT_STATS, HEADER])
 
 
 def source_hash():
@@ -93,7 +97,9 @@ def source_hash():
 def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
     """The six steps of the library build: the main, exact-mode, collect, recording-evaluation and
     exact-evaluation translation units compiled to objects (the latter four with EXACT_FLAGS /
-    COLLECT_FLAGS / COLLECT_FLAGS / EVAL_EXACT_FLAGS), then linked into `out`."""
+    COLLECT_FLAGS / COLLECT_FLAGS / EVAL_EXACT_FLAGS); the last step compiles the statistics collect's
+    unit (COLLECT_FLAGS) and links it with those objects into `out` in one hipcc call. The flags of
+    that call reach only the source it compiles: the objects already hold their code objects."""
     o_main, o_exact, o_coll, o_trace = out + ".main.o", out + ".exact.o", out + ".collect.o", out + ".evaltrace.o"
     o_evx = out + ".evalexact.o"
     c1 = command(resource_usage, o_main, defines, extra, SRC, compile_only=True, preload=preload)
@@ -105,12 +111,13 @@ def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
                  preload=preload)
     c5 = command(resource_usage, o_evx, defines, list(extra) + EVAL_EXACT_FLAGS, SRC_EVAL_EXACT, compile_only=True,
                  preload=preload)
-    c6 = [hipcc(), "--offload-arch=%s" % ARCH, "-shared", "-fPIC", "-o", out, o_main, o_exact, o_coll, o_trace, o_evx]
+    objs = [o_main, o_exact, o_coll, o_trace, o_evx]
+    c6 = command(resource_usage, out, defines, list(extra) + COLLECT_FLAGS + objs, SRC_COLLECT_STATS, preload=preload)
     return [c1, c2, c3, c4, c5, c6]
 
 
 def build_lib(out=OUT, defines=(), extra=(), resource_usage=False, verbose=True, preload=4):
-    """Compile the five translation units (in parallel) and link `out`."""
+    """Compile five translation units to objects (in parallel), then the sixth with the link of `out`."""
     cmds = commands(resource_usage, out, defines, extra, preload=preload)
     if verbose:
         for c in cmds:

@@ -1174,6 +1174,15 @@ struct EvalExactLaunch {
     double* state64;
     void* stream;
 };
+// ... and where rr_rollout_collect_stats's two kernels put the statistics (rr_rollout_stats,
+// rocket_hip.h, plus the row count), beside the collect's EnvLaunch / RolloutIO
+struct CollectStatsIO {
+    uint64_t* partials;      // [rows][RR_RSTAT_SLOTS], 128-B aligned
+    uint64_t* out;           // [RR_RSTAT_SLOTS]
+    uint64_t* accum;         // [RR_RSTAT_SLOTS] or nullptr
+    uint32_t rows;           // ceil(n / 64): the collect's live waves
+};
+static_assert(std::is_trivially_copyable_v<CollectStatsIO>, "CollectStatsIO crosses TUs by memcpy");
 static_assert(std::is_trivially_copyable_v<EvalExactLaunch>, "EvalExactLaunch crosses TUs by memcpy");
 static_assert(std::is_trivially_copyable_v<EnvLaunch>, "EnvLaunch crosses TUs by memcpy");
 static_assert(std::is_trivially_copyable_v<ExactLaunch>, "ExactLaunch crosses TUs by memcpy");
@@ -1192,15 +1201,16 @@ inline T from_unit(const void* p)
 // The hidden entry points (not part of the C-ABI) through which the main translation unit launches
 // the kernels compiled in the others. Defined in rocket_exact.hip / rocket_collect.hip /
 // eval_trace/rocket_eval_trace.hip (rrc_launch_eval_trace) / eval_exact/rocket_eval_exact.hip
-// (rrx_launch_eval_exact); the
+// (rrx_launch_eval_exact) / collect_stats/rocket_collect_stats.hip (rrc_launch_collect_stats); the
 // main TU adds weak stand-ins, so that a library built from rocket_hip.hip alone still loads.
 // launch points to the caller's ExactLaunch / EnvLaunch / EvalExactLaunch / PpoLaunch, io to its
-// StepIO / RolloutIO / EvalIO, trace to its EvalTraceIO.
+// StepIO / RolloutIO / EvalIO, trace to its EvalTraceIO, stats to its CollectStatsIO.
 extern "C" {
 __attribute__((visibility("hidden"))) int rrx_launch_exact(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrx_launch_eval_exact(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrc_launch_collect(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrc_launch_eval(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrc_launch_eval_trace(const void* launch, const void* io, const void* trace);
+__attribute__((visibility("hidden"))) int rrc_launch_collect_stats(const void* launch, const void* io, const void* stats);
 __attribute__((visibility("hidden"))) int rrc_launch_learner(const void* launch, void* stream);
 }

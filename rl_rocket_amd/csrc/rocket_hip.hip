@@ -366,7 +366,7 @@ __global__ __launch_bounds__(kBlock) void narrow_kernel(const double* src, float
 
 // defined by the exact / collect / recording translation units (declared hidden in rocket_device.h);
 // these weak stand-ins (a library built from this file alone, e.g. a tools/ A/B variant) make
-// RR_INT_DOPRI5 steps, rr_rollout_collect, rr_policy_evaluate(_trace / _exact) and the learner fail loudly
+// RR_INT_DOPRI5 steps, rr_rollout_collect(_stats), rr_policy_evaluate(_trace / _exact) and the learner fail loudly
 // instead of failing to load
 constexpr int kNoUnit = (int)hipErrorInvalidDeviceFunction;
 extern "C" {
@@ -375,6 +375,7 @@ __attribute__((weak)) int rrx_launch_eval_exact(const void*, const void*) { retu
 __attribute__((weak)) int rrc_launch_collect(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval_trace(const void*, const void*, const void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_collect_stats(const void*, const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_learner(const void*, void*) { return kNoUnit; }
 }
 
@@ -1355,7 +1356,7 @@ int rr_policy_bootstrap(const float* params, int obs_dim, int act_dim, int preci
 
 namespace {
 int launch_rollout(rr_env* e, const char* who, bool multi, const float* params, int precision, uint64_t seed,
-                   const uint64_t* iter, RolloutIO& io, void* stream)
+                   const uint64_t* iter, RolloutIO& io, void* stream, const CollectStatsIO* stats = nullptr)
 {
     const std::string w = std::string(who) + ": ";
     if (!params || !iter || !io.buf_obs || !io.buf_act || !io.buf_val || !io.buf_logp || !io.buf_start ||
@@ -1382,7 +1383,9 @@ int launch_rollout(rr_env* e, const char* who, bool multi, const float* params, 
     // The collect kernel (MULTI) lives in the third translation unit (rocket_collect.hip), compiled
     // with the MFMA accumulators in VGPRs (rl_rocket_amd/build.py COLLECT_FLAGS).
     hipError_t err = hipSuccess;
-    if (multi) {
+    if (multi && stats) {  // rr_rollout_collect_stats (collect_stats/rocket_collect_stats.hip): two launches
+        err = (hipError_t)rrc_launch_collect_stats(&L, &io, stats);
+    } else if (multi) {
         err = (hipError_t)rrc_launch_collect(&L, &io);
     } else {
         dispatch_env_prec(L.model, L.integ, L.prec, [&](auto m, auto i, auto p) {
@@ -1457,6 +1460,46 @@ int rr_rollout_collect(rr_env* e, const float* params, int precision, uint64_t s
     io.gamma64 = gamma;
     io.lam = gae_lambda;
     return launch_rollout(e, "rr_rollout_collect", true, params, precision, seed, iter, io, stream);
+}
+
+int64_t rr_rollout_stats_rows(int64_t n) { return n <= 0 ? 0 : (n + kWave - 1) / kWave; }
+
+int rr_rollout_collect_stats(rr_env* e, const float* params, int precision, uint64_t seed, const uint64_t* iter,
+                             int n_steps, double gamma, double gae_lambda, float* buf_obs, float* buf_action,
+                             float* buf_value, float* buf_log_prob, float* buf_start, float* buf_reward,
+                             float* buf_advantage, float* buf_return, float* last_value, float* last_done,
+                             float* last_start, float* obs, float* reward, uint8_t* done, uint8_t* truncated,
+                             float* terms, const rr_rollout_stats* stats, void* stream)
+{
+    const char* who = "rr_rollout_collect_stats";
+    const std::string w = std::string(who) + ": ";
+    if (!e) return fail(RR_EINVAL, w + "null handle");
+    if (n_steps <= 0) return fail(RR_EINVAL, w + "n_steps must be positive");
+    if (!stats || !stats->partials || !stats->out) return fail(RR_EINVAL, w + "stats, stats->partials and stats->out must not be null");
+    if (((uintptr_t)stats->partials & 127) != 0) return fail(RR_EINVAL, w + "stats->partials must be 128-B aligned");
+    if ((((uintptr_t)stats->out | (uintptr_t)stats->accum) & 7) != 0)
+        return fail(RR_EINVAL, w + "stats->out and stats->accum must be 8-B aligned");
+    if (!buf_advantage || !buf_return)
+        return fail(RR_EINVAL, w + "buf_advantage and buf_return are required (the sample sums follow the GAE scan)");
+    if (!(e->p.flags & RR_FLAG_EPISODE_STATS))
+        return fail(RR_EINVAL, w + "the handle needs RR_FLAG_EPISODE_STATS (the running return crosses launches)");
+    if (!(e->p.flags & RR_FLAG_AUTO_RESET))
+        return fail(RR_EINVAL, w + "the handle needs RR_FLAG_AUTO_RESET (episodes follow one another)");
+    RolloutIO io = rollout_io(buf_obs, buf_action, buf_value, buf_log_prob, buf_start, buf_reward, obs, reward, done,
+                              truncated, terms);
+    io.buf_adv = buf_advantage;
+    io.buf_ret = buf_return;
+    io.last_value = last_value;
+    io.last_done = last_done;
+    io.last_start = last_start;
+    io.t = 0;
+    io.T = (uint32_t)n_steps;
+    io.gamma = (float)gamma;  // as rr_rollout_collect
+    io.gamma64 = gamma;
+    io.lam = gae_lambda;
+    const CollectStatsIO sio = {(uint64_t*)stats->partials, (uint64_t*)stats->out, (uint64_t*)stats->accum,
+                                (uint32_t)rr_rollout_stats_rows(e->n)};
+    return launch_rollout(e, who, true, params, precision, seed, iter, io, stream, &sio);
 }
 
 namespace {

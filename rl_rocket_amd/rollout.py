@@ -279,10 +279,15 @@ class DeviceRollout:
     ``policy_dtype="bf16"`` (fused only, opt-in) runs the towers on bf16 MFMA with fp32
     accumulation: actions / values / log-probs then differ from the fp32 policy by the bf16
     rounding of obs, weights and the first hidden layer (the stored log-probs are those of
-    the bf16 mean; PPO's first-epoch ratio starts within ~1e-3 of 1 instead of at 1)."""
+    the bf16 mean; PPO's first-epoch ratio starts within ~1e-3 of 1 instead of at 1).
+    ``stats=True`` (one-launch path only, a batch with ``episode_stats=True`` and auto-reset) makes
+    ``collect`` account for every episode the rollout finishes and for the samples' explained
+    variance in the same launch (``rr_rollout_collect_stats``; the rollout itself is bitwise
+    unchanged): ``ro.stats.last()`` / ``ro.stats.window()`` return SB3's ``rollout/*`` figures and
+    ``train/explained_variance`` (``rollout_stats.RolloutStats``)."""
 
     def __init__(self, batch, policy, n_steps=16, gamma=0.99, gae_lambda=0.95, generator=None, fused=None,
-                 seed=0, policy_dtype="fp32", one_launch=None, per_step=False):
+                 seed=0, policy_dtype="fp32", one_launch=None, per_step=False, stats=False):
         self.env, self.policy = batch, policy
         self.n_steps, self.gamma, self.lam = n_steps, gamma, gae_lambda
         n, ns, na = batch.num_envs, batch.state_dim, batch.action_dim
@@ -319,6 +324,15 @@ class DeviceRollout:
             raise ValueError("one_launch needs the fused policy and an RK4 / Euler env")
         self.one_launch = bool(one_launch)
         self.per_step = bool(per_step) or not self.one_launch  # one_launch + not per_step: rr_rollout_collect
+        self.stats = None
+        if stats:
+            from . import _lib
+
+            if not self.one_launch or self.per_step:
+                raise ValueError("stats=True needs the one-launch collect (fused policy, RK4 / Euler env, not per_step)")
+            flags = int(batch.params.flags)
+            if not flags & _lib.RR_FLAG_EPISODE_STATS or not flags & _lib.RR_FLAG_AUTO_RESET:
+                raise ValueError("stats=True needs a batch created with episode_stats=True and auto_reset=True")
         if self.fused:
             from . import _lib
 
@@ -337,6 +351,10 @@ class DeviceRollout:
             _lib.check(self._lib.rr_get_buffers(batch._h, ctypes.byref(bufs)), "rr_get_buffers")
             self._term_obs = ctypes.c_void_p(bufs.terminal_obs)
             batch.done.fill_(1)  # SB3: _last_episode_starts = ones before the first rollout
+            if stats:
+                from .rollout_stats import RolloutStats
+
+                self.stats = RolloutStats(n, dev, self._lib)
 
     @torch.no_grad()
     def collect(self):
@@ -382,6 +400,17 @@ class DeviceRollout:
         stream = c.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
         it, obs, done = p(self.iter), p(env.obs), p(env.done)
         prec = self._pack.prec
+        if self.stats is not None:
+            st = self.stats.struct()
+            _lib.check(lib.rr_rollout_collect_stats(env._h, params, prec, self.seed, it, self.n_steps, self.gamma,
+                                                    self.lam, p(self.obs), p(self.actions), p(self.values),
+                                                    p(self.log_probs), p(self.starts), p(self.rewards),
+                                                    p(self.advantages), p(self.returns), p(self.last_value),
+                                                    p(self.last_done), p(self.last_start), obs, p(env.reward), done,
+                                                    p(env.truncated), p(env.terms), c.byref(st), stream),
+                       "rr_rollout_collect_stats")
+            self.iter.add_(1)
+            return
         if self.one_launch and not self.per_step:
             _lib.check(lib.rr_rollout_collect(env._h, params, prec, self.seed, it, self.n_steps, self.gamma, self.lam,
                                               p(self.obs), p(self.actions), p(self.values), p(self.log_probs),
@@ -912,9 +941,11 @@ class GraphedPPOUpdate:
         pol = self.policy
         if self._update is not None:
             st = self._update(i, self._mb(k + 1) if k + 1 < self.n_mb else None, chained=k > 0)
+            self._more = (st[3], st[4])
             return {"policy_loss": st[0], "value_loss": st[1], "entropy": st[2]}
         if self.fused:
             st = self._grad(i)
+            self._more = (st[3], st[4])
             if self.group is not None:
                 _allreduce_grads(self.params, self.group)
             if self._adam is not None:
@@ -938,7 +969,18 @@ class GraphedPPOUpdate:
             _allreduce_grads(self.params, self.group)
         torch.nn.utils.clip_grad_norm_(pol.parameters(), max_grad_norm)
         self.optimizer.step()
+        with torch.no_grad():  # SB3 1.6 PPO.train's clip_fraction and approx_kl, as rr_ppo_grad's stats[3:5]
+            log_ratio = lp - self.old_lp[i]
+            self._more = ((torch.abs(ratio - 1) > clip_range).float().mean(), ((ratio - 1) - log_ratio).mean())
         return {"policy_loss": pg.detach(), "value_loss": vf.detach(), "entropy": -ent.detach()}
+
+    def last_stats(self):
+        """The last minibatch step's five figures as ``train/*`` keys: ``update``'s three and the
+        ``clip_fraction`` / ``approx_kl`` the step computes beside them. One iteration's log dict is
+        ``ro.stats.last() | upd.last_stats()``."""
+        out = {"train/" + k: float(v) for k, v in self.stats.items()}
+        out["train/clip_fraction"], out["train/approx_kl"] = (float(v) for v in self._more)
+        return out
 
     def _perm_streams(self):
         dev = self.obs.device
