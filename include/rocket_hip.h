@@ -612,6 +612,70 @@ int rr_ppo_update(int obs_dim, int act_dim, float* const* params, float* const* 
                   float vf_coef, float max_grad_norm, const float* lr, double beta1, double beta2, float eps,
                   float* stats, uint32_t flags, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* rr_ppo_update with the options of SB3 1.6's PPO.__init__ that it fixes, and PPO.train's early stop
+ * and logging carried on the device: what replaces, per minibatch of PPO.train,
+ *   values_pred = old_values + clamp(values - old_values, -clip_range_vf, clip_range_vf)
+ *                                                         (clip_range_vf > 0; value_loss uses values_pred),
+ *   `if self.normalize_advantage`                         (0: the loss takes advantages[idx] as they are),
+ *   `if self.target_kl is not None and approx_kl_div > 1.5 * self.target_kl: continue_training = False;
+ *    break`, and with it `if not continue_training: break` of the epoch loop,
+ *   the appends to pg_losses / value_losses / entropy_losses / clip_fractions / approx_kl_divs that
+ *   train() averages into train/policy_gradient_loss, value_loss, entropy_loss, clip_fraction, approx_kl.
+ * Arguments as rr_ppo_update's, plus old_values [*] (the rollout's values, gathered by idx; required
+ * with clip_range_vf > 0, else may be NULL), options (host), control (device, RR_PPO_CTL_SLOTS
+ * floats, 16-B aligned, or NULL without target_kl and train_stats) and the flag RR_PPO_EPOCH_START
+ * (this call is an epoch's first minibatch: the approx_kl mean restarts, the epoch count advances).
+ * stats may be NULL.
+ *
+ * The control block is the caller's: zero it (hipMemsetAsync) before the first minibatch of a
+ * train() call. While RR_PPO_CTL_STOP is 0 every call evaluates its minibatch, adds its loss figures
+ * to the running sums and counts it (RR_PPO_CTL_EVALS). If its approx_kl > 1.5 target_kl the call
+ * applies no optimizer step: parameters, exp_avg, exp_avg_sq and step stay as they were (grads are
+ * unspecified), and RR_PPO_CTL_STOP becomes 1. Otherwise it steps and counts the step
+ * (RR_PPO_CTL_STEPS). With RR_PPO_CTL_STOP set every call is a no-op for parameters, optimizer
+ * state, stats, the workspace and the block itself (its kernels read the word and return), so the
+ * rest of a captured epoch, and the epochs after it, cost their launches only. SB3's figures:
+ * train/approx_kl = KL_SUM / KL_COUNT (the last, possibly partial, epoch), the others SUM_* / EVALS
+ * (train/entropy_loss = -SUM_ENTROPY / EVALS), the epoch train() stopped in = EPOCHS - 1.
+ *
+ * With clip_range_vf = 0, target_kl = 0 and normalize_advantage = 1 the call computes bitwise what
+ * rr_ppo_update computes, chained or not. Four launches (three chained) on `stream`, capturable in a
+ * graph; deterministic: every sum in a fixed order, every word of the block with one writer per
+ * launch. RR_EINVAL before any launch for what rr_ppo_update refuses and for: NaN or negative
+ * clip_range_vf / target_kl, clip_range_vf > 0 without old_values, target_kl > 0 or train_stats
+ * without control, unknown flag bits. workspace: rr_ppo_update_opts_workspace_size bytes. */
+#define RR_PPO_EPOCH_START 0x2u
+enum {
+    RR_PPO_CTL_STOP = 0,     /* 1 after the minibatch whose approx_kl passed 1.5 target_kl */
+    RR_PPO_CTL_DECIDE,       /* the last evaluated minibatch's decision (the optimizer launch reads it) */
+    RR_PPO_CTL_STEPS,        /* optimizer steps applied */
+    RR_PPO_CTL_EVALS,        /* minibatches evaluated */
+    RR_PPO_CTL_EPOCHS,       /* epochs begun (calls with RR_PPO_EPOCH_START evaluated) */
+    RR_PPO_CTL_SUM_POLICY,   /* sums over the evaluated minibatches: policy_loss */
+    RR_PPO_CTL_SUM_VALUE,    /* value_loss */
+    RR_PPO_CTL_SUM_ENTROPY,  /* entropy */
+    RR_PPO_CTL_SUM_CLIP,     /* clip_fraction */
+    RR_PPO_CTL_KL_SUM,       /* approx_kl summed over the current epoch's minibatches */
+    RR_PPO_CTL_KL_COUNT,     /* and their number */
+    RR_PPO_CTL_KL_LAST,      /* the last evaluated minibatch's approx_kl */
+    RR_PPO_CTL_SLOTS = 16    /* floats: a block is 64 bytes */
+};
+typedef struct rr_ppo_options {
+    float clip_range_vf;          /* 0: no value clip (negative or NaN is refused) */
+    float target_kl;              /* 0: no KL stop */
+    int32_t normalize_advantage;  /* SB3's default: 1 */
+    int32_t train_stats;          /* 1: the caller reads the running sums (needs control) */
+} rr_ppo_options;
+int rr_ppo_update_opts_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes);
+int rr_ppo_update_opts(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* exp_avg,
+                       float* const* exp_avg_sq, float* const* step, const float* obs, const float* actions,
+                       const float* old_log_prob, const float* advantages, const float* returns,
+                       const float* old_values, const int64_t* idx, int64_t batch, const int64_t* next_idx,
+                       int64_t next_batch, float clip_range, float ent_coef, float vf_coef, float max_grad_norm,
+                       const float* lr, double beta1, double beta2, float eps, const rr_ppo_options* options,
+                       float* control, float* stats, uint32_t flags, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

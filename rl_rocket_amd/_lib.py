@@ -111,6 +111,26 @@ class RrRolloutStats(ctypes.Structure):
 RR_RSTAT_INT_SLOTS = (0, 1, 2, 3, 4, 5, 6, 15)
 
 
+class RrPpoOptions(ctypes.Structure):
+    """Mirror of ``rr_ppo_options`` (host record of rr_ppo_update_opts; 0 switches an option off)."""
+
+    _fields_ = [
+        ("clip_range_vf", ctypes.c_float),
+        ("target_kl", ctypes.c_float),
+        ("normalize_advantage", ctypes.c_int32),
+        ("train_stats", ctypes.c_int32),
+    ]
+
+
+# rr_ppo_update / rr_ppo_update_opts flags and the slots of the latter's control block (rocket_hip.h
+# RR_PPO_CTL_*): 16 floats
+RR_PPO_CHAINED, RR_PPO_EPOCH_START = 0x1, 0x2
+(RR_PPO_CTL_STOP, RR_PPO_CTL_DECIDE, RR_PPO_CTL_STEPS, RR_PPO_CTL_EVALS, RR_PPO_CTL_EPOCHS, RR_PPO_CTL_SUM_POLICY,
+ RR_PPO_CTL_SUM_VALUE, RR_PPO_CTL_SUM_ENTROPY, RR_PPO_CTL_SUM_CLIP, RR_PPO_CTL_KL_SUM, RR_PPO_CTL_KL_COUNT,
+ RR_PPO_CTL_KL_LAST) = range(12)
+RR_PPO_CTL_SLOTS = 16
+
+
 class RrEvalTrace(ctypes.Structure):
     """Mirror of ``rr_eval_trace`` (device pointers; ``action`` / ``terms`` may be NULL)."""
 
@@ -188,6 +208,11 @@ SIGNATURES = {
                                      ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _P,
                                      ctypes.c_double, ctypes.c_double, ctypes.c_float, _P, ctypes.c_uint32, _P,
                                      ctypes.c_int64, _P]),
+    "rr_ppo_update_opts_workspace_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P]),
+    "rr_ppo_update_opts": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 12 +
+                           [ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                            ctypes.c_float, _P, ctypes.c_double, ctypes.c_double, ctypes.c_float,
+                            ctypes.POINTER(RrPpoOptions), _P, _P, ctypes.c_uint32, _P, ctypes.c_int64, _P]),
 }
 
 _LIB = None

@@ -1201,7 +1201,8 @@ inline T from_unit(const void* p)
 // The hidden entry points (not part of the C-ABI) through which the main translation unit launches
 // the kernels compiled in the others. Defined in rocket_exact.hip / rocket_collect.hip /
 // eval_trace/rocket_eval_trace.hip (rrc_launch_eval_trace) / eval_exact/rocket_eval_exact.hip
-// (rrx_launch_eval_exact) / collect_stats/rocket_collect_stats.hip (rrc_launch_collect_stats); the
+// (rrx_launch_eval_exact) / collect_stats/rocket_collect_stats.hip (rrc_launch_collect_stats) /
+// ppo_opts/rocket_ppo_opts.hip (rrc_launch_learner_opts, a PpoOptsLaunch); the
 // main TU adds weak stand-ins, so that a library built from rocket_hip.hip alone still loads.
 // launch points to the caller's ExactLaunch / EnvLaunch / EvalExactLaunch / PpoLaunch, io to its
 // StepIO / RolloutIO / EvalIO, trace to its EvalTraceIO, stats to its CollectStatsIO.
@@ -1213,4 +1214,5 @@ __attribute__((visibility("hidden"))) int rrc_launch_eval(const void* launch, co
 __attribute__((visibility("hidden"))) int rrc_launch_eval_trace(const void* launch, const void* io, const void* trace);
 __attribute__((visibility("hidden"))) int rrc_launch_collect_stats(const void* launch, const void* io, const void* stats);
 __attribute__((visibility("hidden"))) int rrc_launch_learner(const void* launch, void* stream);
+__attribute__((visibility("hidden"))) int rrc_launch_learner_opts(const void* launch, void* stream);
 }

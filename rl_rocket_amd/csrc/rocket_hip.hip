@@ -24,6 +24,7 @@
 // (the tools/ A/B variants): see the weak stand-ins below.
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -377,6 +378,7 @@ __attribute__((weak)) int rrc_launch_eval(const void*, const void*) { return kNo
 __attribute__((weak)) int rrc_launch_eval_trace(const void*, const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_collect_stats(const void*, const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_learner(const void*, void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_learner_opts(const void*, void*) { return kNoUnit; }
 }
 
 namespace {
@@ -1749,34 +1751,37 @@ int rr_ppo_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_
     return RR_OK;
 }
 
-int rr_ppo_update(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* exp_avg,
-                  float* const* exp_avg_sq, float* const* step, const float* obs, const float* actions,
-                  const float* old_log_prob, const float* advantages, const float* returns, const int64_t* idx,
-                  int64_t batch, const int64_t* next_idx, int64_t next_batch, float clip_range, float ent_coef,
-                  float vf_coef, float max_grad_norm, const float* lr, double beta1, double beta2, float eps,
-                  float* stats, uint32_t flags, void* workspace, int64_t workspace_bytes, void* stream)
+namespace {
+// rr_ppo_update's argument checks and launch record, for it and rr_ppo_update_opts (`who` names the
+// entry point in the error text, known_flags its flag bits; ws_need its workspace size)
+int ppo_update_record(const char* who, PpoLaunch& L, int obs_dim, int act_dim, float* const* params,
+                      float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, float* const* step,
+                      const float* obs, const float* actions, const float* old_log_prob, const float* advantages,
+                      const float* returns, const int64_t* idx, int64_t batch, const int64_t* next_idx,
+                      int64_t next_batch, float clip_range, float ent_coef, float vf_coef, float max_grad_norm,
+                      const float* lr, double beta1, double beta2, float eps, float* stats, uint32_t flags,
+                      uint32_t known_flags, void* workspace, int64_t workspace_bytes, int64_t ws_need)
 {
-    int64_t need = 0, ppo_bytes = 0;
-    int rc = rr_ppo_update_workspace_size(obs_dim, act_dim, batch, &need);
-    if (rc != RR_OK) return rc;
+    const std::string w = std::string(who) + ": ";
+    int64_t ppo_bytes = 0;
     rr_ppo_workspace_size(obs_dim, act_dim, batch, &ppo_bytes);
     if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !obs || !actions || !old_log_prob || !advantages ||
         !returns || !idx || !lr || !workspace)
-        return fail(RR_EINVAL, "rr_ppo_update: null argument");
-    if (workspace_bytes < need) return fail(RR_EINVAL, "rr_ppo_update: workspace smaller than rr_ppo_update_workspace_size");
-    if (((uintptr_t)workspace & 15) != 0) return fail(RR_EINVAL, "rr_ppo_update: workspace must be 16-B aligned");
-    if (!(clip_range >= 0.0f)) return fail(RR_EINVAL, "rr_ppo_update: clip_range must be >= 0");
-    if (flags & ~(uint32_t)RR_PPO_CHAINED) return fail(RR_EINVAL, "rr_ppo_update: unknown flag bits");
+        return fail(RR_EINVAL, (w + "null argument").c_str());
+    if (workspace_bytes < ws_need) return fail(RR_EINVAL, (w + "workspace smaller than " + who + "_workspace_size").c_str());
+    if (((uintptr_t)workspace & 15) != 0) return fail(RR_EINVAL, (w + "workspace must be 16-B aligned").c_str());
+    if (!(clip_range >= 0.0f)) return fail(RR_EINVAL, (w + "clip_range must be >= 0").c_str());
+    if (flags & ~known_flags) return fail(RR_EINVAL, (w + "unknown flag bits").c_str());
     if (next_idx && !(next_batch >= 2 && next_batch <= batch))
-        return fail(RR_EINVAL, "rr_ppo_update: next_batch must be in [2, batch]");
+        return fail(RR_EINVAL, (w + "next_batch must be in [2, batch]").c_str());
     const int na = act_dim, no = obs_dim;
     const int64_t numel[13] = {64 * no, 64, 64 * 64, 64, 64 * no, 64, 64 * 64, 64, 64 * na, na, 64, 1, na};
-    PpoLaunch L = {};
+    L = {};
     L.op = 1;
     L.a.n = 13;
     for (int k = 0; k < 13; ++k) {
         if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || !step[k])
-            return fail(RR_EINVAL, "rr_ppo_update: null parameter, gradient or optimizer-state tensor");
+            return fail(RR_EINVAL, (w + "null parameter, gradient or optimizer-state tensor").c_str());
         L.ps.p[k] = params[k];
         L.pg.p[k] = grads[k];
         L.a.param[k] = params[k];
@@ -1810,9 +1815,88 @@ int rr_ppo_update(int obs_dim, int act_dim, float* const* params, float* const* 
     L.w2 = (float)(1.0 - beta2);
     L.eps = eps;
     L.stats = stats;
-    L.flags = flags;
+    L.flags = flags & RR_PPO_CHAINED;
+    return RR_OK;
+}
+}  // namespace
+
+int rr_ppo_update(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* exp_avg,
+                  float* const* exp_avg_sq, float* const* step, const float* obs, const float* actions,
+                  const float* old_log_prob, const float* advantages, const float* returns, const int64_t* idx,
+                  int64_t batch, const int64_t* next_idx, int64_t next_batch, float clip_range, float ent_coef,
+                  float vf_coef, float max_grad_norm, const float* lr, double beta1, double beta2, float eps,
+                  float* stats, uint32_t flags, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    int64_t need = 0;
+    int rc = rr_ppo_update_workspace_size(obs_dim, act_dim, batch, &need);
+    if (rc != RR_OK) return rc;
+    PpoLaunch L;
+    rc = ppo_update_record("rr_ppo_update", L, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step, obs, actions,
+                           old_log_prob, advantages, returns, idx, batch, next_idx, next_batch, clip_range, ent_coef,
+                           vf_coef, max_grad_norm, lr, beta1, beta2, eps, stats, flags, RR_PPO_CHAINED, workspace,
+                           workspace_bytes, need);
+    if (rc != RR_OK) return rc;
     const hipError_t err = (hipError_t)rrc_launch_learner(&L, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update: launch");
+}
+
+static_assert(ppo::kStop == RR_PPO_CTL_STOP && ppo::kDecide == RR_PPO_CTL_DECIDE && ppo::kSteps == RR_PPO_CTL_STEPS &&
+                  ppo::kEvals == RR_PPO_CTL_EVALS && ppo::kEpochs == RR_PPO_CTL_EPOCHS &&
+                  ppo::kSumPg == RR_PPO_CTL_SUM_POLICY && ppo::kSumVf == RR_PPO_CTL_SUM_VALUE &&
+                  ppo::kSumEnt == RR_PPO_CTL_SUM_ENTROPY && ppo::kSumClip == RR_PPO_CTL_SUM_CLIP &&
+                  ppo::kKlSum == RR_PPO_CTL_KL_SUM && ppo::kKlCount == RR_PPO_CTL_KL_COUNT &&
+                  ppo::kKlLast == RR_PPO_CTL_KL_LAST && ppo::kKlLast < RR_PPO_CTL_SLOTS,
+              "the kernels' control-block slots are the header's");
+
+int rr_ppo_update_opts_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
+{
+    int64_t upd = 0;
+    if (!ppo_part_floats(obs_dim, act_dim))
+        return fail(RR_EINVAL, "rr_ppo_update_opts_workspace_size: supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
+    if (batch < 2 || !bytes) return fail(RR_EINVAL, "rr_ppo_update_opts_workspace_size: batch >= 2 and bytes required");
+    rr_ppo_update_workspace_size(obs_dim, act_dim, batch, &upd);
+    *bytes = upd + 32;  // + 8 floats: the call's statistics when the caller passes none (the control block sums them)
+    return RR_OK;
+}
+
+int rr_ppo_update_opts(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* exp_avg,
+                       float* const* exp_avg_sq, float* const* step, const float* obs, const float* actions,
+                       const float* old_log_prob, const float* advantages, const float* returns,
+                       const float* old_values, const int64_t* idx, int64_t batch, const int64_t* next_idx,
+                       int64_t next_batch, float clip_range, float ent_coef, float vf_coef, float max_grad_norm,
+                       const float* lr, double beta1, double beta2, float eps, const rr_ppo_options* options,
+                       float* control, float* stats, uint32_t flags, void* workspace, int64_t workspace_bytes,
+                       void* stream)
+{
+    int64_t need = 0, upd = 0;
+    int rc = rr_ppo_update_opts_workspace_size(obs_dim, act_dim, batch, &need);
+    if (rc != RR_OK) return rc;
+    rr_ppo_update_workspace_size(obs_dim, act_dim, batch, &upd);
+    PpoOptsLaunch O = {};
+    rc = ppo_update_record("rr_ppo_update_opts", O.base, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step, obs,
+                           actions, old_log_prob, advantages, returns, idx, batch, next_idx, next_batch, clip_range,
+                           ent_coef, vf_coef, max_grad_norm, lr, beta1, beta2, eps, stats, flags,
+                           RR_PPO_CHAINED | RR_PPO_EPOCH_START, workspace, workspace_bytes, need);
+    if (rc != RR_OK) return rc;
+    if (!options) return fail(RR_EINVAL, "rr_ppo_update_opts: null options");
+    // NaN fails both comparisons' complements: !(x >= 0) is true for NaN and for negatives
+    if (!(options->clip_range_vf >= 0.0f)) return fail(RR_EINVAL, "rr_ppo_update_opts: clip_range_vf must be >= 0 (0: off)");
+    if (!(options->target_kl >= 0.0f)) return fail(RR_EINVAL, "rr_ppo_update_opts: target_kl must be >= 0 (0: off)");
+    if (options->clip_range_vf > 0.0f && !old_values)
+        return fail(RR_EINVAL, "rr_ppo_update_opts: clip_range_vf needs old_values");
+    if (options->target_kl > 0.0f && !control) return fail(RR_EINVAL, "rr_ppo_update_opts: target_kl needs a control block");
+    if (options->train_stats && !control)
+        return fail(RR_EINVAL, "rr_ppo_update_opts: train_stats needs a control block");
+    if (((uintptr_t)control & 15) != 0) return fail(RR_EINVAL, "rr_ppo_update_opts: control block must be 16-B aligned");
+    O.old_values = old_values;
+    O.clip_vf = options->clip_range_vf;
+    O.normalize = options->normalize_advantage != 0;
+    O.ctl.ctl = control;
+    O.ctl.kl_limit = options->target_kl > 0.0f ? 1.5f * options->target_kl : HUGE_VALF;
+    O.ctl.epoch_start = (flags & RR_PPO_EPOCH_START) != 0;
+    if (!stats) O.base.stats = (float*)((char*)workspace + upd);
+    const hipError_t err = (hipError_t)rrc_launch_learner_opts(&O, stream);
+    return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_opts: launch");
 }
 
 

@@ -38,6 +38,11 @@
 // The types and the kernel templates are here for both translation units that include this file;
 // the kernels are instantiated and launched in the collect TU (rocket_collect.hip,
 // rrc_launch_learner), which also defines adam_norm_kernel / adam_step_kernel.
+// The kernels' bodies carry compile-time options that are all off in the kernels here: the
+// value-function clip (VCLIP), raw advantages (NORM false) and the control block of
+// rr_ppo_update_opts (CTL: stop word, running statistics). ppo_opts/rocket_ppo_opts.hip instantiates
+// them with the options on, in kernels of its own: ppo_prep_body and ppo_grad_tower as functions,
+// the finish and optimizer bodies as included text (rocket_ppo_finish_body.inc).
 #pragma once
 
 #include <type_traits>
@@ -153,12 +158,29 @@ __device__ float pack_value(const PolSrc& src, int tw, int k)
 }
 
 // One tile's gathered inputs (lane: sample j, obs columns 2k + half): x, and for pi the action,
-// old log-prob and raw advantage, for vf the return (in av).
+// old log-prob and raw advantage, for vf the return (in av) and, under the value clip, the
+// rollout's value (in olp).
 template <int OBS, int ACT>
 struct TileIn {
     float x[pol::Layout<OBS, ACT, 0>::KP1];
     float a[ACT];
     float olp, av;
+};
+
+// The control block of rr_ppo_update_opts (rocket_hip.h RR_PPO_CTL_*: these are its slots). Who
+// writes what, so that no block reads a word another block of the same launch writes:
+//   the finish launch  reads kStop; the thread that holds a statistic adds it to that statistic's
+//                      sum, and the approx_kl one also counts the minibatch and the epoch and writes
+//                      kDecide = (approx_kl > 1.5 target_kl);
+//   the optimizer launch  reads kDecide: set, it steps nothing and block 0 commits kStop; clear,
+//                      block 0 counts the step;
+//   the packing and gradient launches  read kStop.
+// kDecide stays set after a stop (the finish launches that would clear it return at kStop).
+enum Ctl { kStop = 0, kDecide, kSteps, kEvals, kEpochs, kSumPg, kSumVf, kSumEnt, kSumClip, kKlSum, kKlCount, kKlLast };
+struct CtlArgs {
+    float* ctl;       // null: no control block
+    float kl_limit;   // 1.5 target_kl, +inf without one
+    int epoch_start;  // this call is an epoch's first minibatch
 };
 
 template <typename T>
@@ -199,9 +221,9 @@ __device__ __forceinline__ void adv_sums(const float* __restrict__ adv, const in
 // them the two towers' packed LDS images (pack[tower * Pack::SIZE + k], one element per thread),
 // which every gradient workgroup then stages with 16-B loads.
 template <int OBS, int ACT>
-__global__ __launch_bounds__(256) void ppo_prep_kernel(const float* __restrict__ adv, const int64_t* __restrict__ idx,
-                                                       int64_t bs, double* __restrict__ part, PolSrc src,
-                                                       float* __restrict__ pack)
+__device__ __forceinline__ void ppo_prep_body(const float* __restrict__ adv, const int64_t* __restrict__ idx,
+                                              int64_t bs, double* __restrict__ part, const PolSrc& src,
+                                              float* __restrict__ pack)
 {
     using K = ppo::Pack<OBS, ACT>;
     if (blockIdx.x >= ppo::kAdvPart) {
@@ -231,17 +253,32 @@ __global__ __launch_bounds__(256) void ppo_prep_kernel(const float* __restrict__
     }
 }
 
+template <int OBS, int ACT>
+__global__ __launch_bounds__(256) void ppo_prep_kernel(const float* __restrict__ adv, const int64_t* __restrict__ idx,
+                                                       int64_t bs, double* __restrict__ part, PolSrc src,
+                                                       float* __restrict__ pack)
+{
+    ppo_prep_body<OBS, ACT>(adv, idx, bs, part, src, pack);
+}
+
 // One workgroup = 4 waves of one tower (blockIdx.y: 0 pi, 1 vf); writes the workgroup's partial
 // gradient vector part[(tower * gridDim.x + blockIdx.x) * Part::SIZE ..]. The tower is a template
 // parameter of the body (ppo_grad_tower<..., 0 / 1>): with it a runtime value, the two towers'
 // gathers shared registers, and the hazard between one tower's in-flight load and the other's
 // zero-initialised destination made every tile wait for its own gather (tools/ppo_stamps.py).
-template <int OBS, int ACT, int TW>
+// VCLIP (SB3's clip_range_vf = clip_vf > 0): the vf tower gathers the rollout's value old_val[r]
+// with the tile's other rows and its head computes
+//   Vc = old + clamp(V - old, -clip_vf, clip_vf), value_loss = mean((ret - Vc)^2),
+//   dV = vf_coef 2 (Vc - ret) / B where -clip_vf <= V - old <= clip_vf (torch's clamp passes the
+//   gradient on the closed interval), else 0.
+// NORM false (normalize_advantage=False): A = adv[idx], the minibatch statistics are not read.
+template <int OBS, int ACT, int TW, bool VCLIP = false, bool NORM = true>
 __device__ __forceinline__ void ppo_grad_tower(
     float* __restrict__ lds, const float* __restrict__ obs, const float* __restrict__ act,
     const float* __restrict__ old_lp, const float* __restrict__ adv, const float* __restrict__ ret,
     const int64_t* __restrict__ idx, int64_t bs, float clip, float vf_coef, const double* __restrict__ adv_part,
-    const float* __restrict__ pack, float* __restrict__ part)
+    const float* __restrict__ pack, float* __restrict__ part, const float* __restrict__ old_val = nullptr,
+    float clip_vf = 0.0f)
 {
     using L = pol::Layout<OBS, ACT, 0>;
     using K = ppo::Pack<OBS, ACT>;
@@ -285,6 +322,7 @@ __device__ __forceinline__ void ppo_grad_tower(
             in.av = adv[r];
         } else {
             in.av = ret[r];
+            if constexpr (VCLIP) in.olp = old_val[r];  // with the tile's other rows: unmasked, one tile ahead
         }
     };
     // Issue order: the first tile's indices, the staging loads, then the first tile's rows (which
@@ -315,7 +353,7 @@ __device__ __forceinline__ void ppo_grad_tower(
     // minibatch advantage statistics (pi): mean, unbiased std
     // (the mean as a float pair: rounded to one float, a mean of 50 over a std of 0.5 moves every A by ~3e-6)
     float a_mean = 0.0f, a_mean_lo = 0.0f, a_den = 1.0f;
-    if (tw == 0) {
+    if (tw == 0 && NORM) {
         double s = 0.0, q = 0.0;
 #pragma unroll
         for (int j = lane; j < ppo::kAdvPart; j += kWave) {
@@ -380,7 +418,9 @@ __device__ __forceinline__ void ppo_grad_tower(
         // heads and the per-sample loss derivatives (both lane halves hold sample j)
         float dh[ACT];
         if (tw == 0) {
-            const float A = valid ? ((in.av - a_mean) - a_mean_lo) / a_den : 0.0f;
+            float A;
+            if constexpr (NORM) A = valid ? ((in.av - a_mean) - a_mean_lo) / a_den : 0.0f;
+            else A = valid ? in.av : 0.0f;
             float lp = 0.0f, d[ACT];
 #pragma unroll
             for (int a = 0; a < ACT; ++a) {
@@ -413,10 +453,21 @@ __device__ __forceinline__ void ppo_grad_tower(
         } else {
             const float v = pol::head_dot<1>(sp + K::HW, h2, 0, half) + sp[K::HB];
             const float R = in.av;
-            dh[0] = valid ? vf_coef * 2.0f * (v - R) * inv_b : 0.0f;
-            if (half == 0) {
-                hb_acc[0] += dh[0];
-                if (valid) st0 += (R - v) * (R - v);
+            if constexpr (VCLIP) {
+                const float dv = v - in.olp;
+                const float vc = in.olp + fminf(fmaxf(dv, -clip_vf), clip_vf);
+                const bool pass = dv >= -clip_vf && dv <= clip_vf;
+                dh[0] = valid && pass ? vf_coef * 2.0f * (vc - R) * inv_b : 0.0f;
+                if (half == 0) {
+                    hb_acc[0] += dh[0];
+                    if (valid) st0 += (R - vc) * (R - vc);
+                }
+            } else {
+                dh[0] = valid ? vf_coef * 2.0f * (v - R) * inv_b : 0.0f;
+                if (half == 0) {
+                    hb_acc[0] += dh[0];
+                    if (valid) st0 += (R - v) * (R - v);
+                }
             }
         }
         RR_ST(3);
@@ -644,95 +695,9 @@ __global__ __launch_bounds__(256) void ppo_finish_kernel(const float* __restrict
                                                          float* __restrict__ stats, float* __restrict__ normw,
                                                          const float* __restrict__ step0)
 {
-    using PT = ppo::Part<OBS, ACT>;
-    static_assert(kFinElems * kFinGroups == 256, "block shape");
-    static_assert(kFinElems == kWave / 2, "the norm sum is a half-wave sum");
-    __shared__ float red[kFinGroups][kFinElems];
-    const int tw = blockIdx.y;
-    const int l = threadIdx.x % kFinElems, grp = threadIdx.x / kFinElems;
-    const int e = blockIdx.x * kFinElems + l;
-    float s = 0.0f;
-    if (e < PT::SIZE) {
-        const float* p = part + (int64_t)tw * nwg * PT::SIZE + e;
-        float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        int w = grp;
-        // four rounds' 16 loads in flight at once, then added in the rounds' order
-        for (; w + 15 * kFinGroups < nwg; w += 16 * kFinGroups) {
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = p[(int64_t)(w + u * kFinGroups) * PT::SIZE];
-            __builtin_amdgcn_sched_barrier(0);  // the scheduler otherwise waits for each load in turn
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int u = 0; u < 4; ++u) a[u] += v[4 * r + u];
-        }
-        for (; w + 3 * kFinGroups < nwg; w += 4 * kFinGroups)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) a[u] += p[(int64_t)(w + u * kFinGroups) * PT::SIZE];
-        for (; w < nwg; w += kFinGroups) a[0] += p[(int64_t)w * PT::SIZE];
-        s = (a[0] + a[1]) + (a[2] + a[3]);
-    }
-    red[grp][l] = s;
-    __syncthreads();
-    if (grp != 0) return;
-    float v = 0.0f;
-#pragma unroll
-    for (int g = 0; g < kFinGroups; ++g) v += red[g][l];
-    float* out = nullptr;  // where element e's gradient goes (none: padding, statistics)
-    float* const* G = dst.p + 4 * tw;  // W1 b1 W2 b2 of this tower
-    if (e >= PT::SIZE) {
-    } else if (e < PT::W1) {
-        const int lane = e % 64, reg = (e / 64) % 16, blk = e / 1024;
-        const int u2 = 32 * (blk >> 1) + ppo::drow(reg, lane >> 5), u1 = 32 * (blk & 1) + (lane & 31);
-        out = &G[2][u2 * 64 + u1];
-    } else if (e < PT::B2) {
-        const int i = e - PT::W1, lane = i % 64, reg = (i / 64) % 16, m = i / 1024;
-        const int u1 = 32 * m + ppo::drow(reg, lane >> 5), col = lane & 31;
-        if (col < OBS) out = &G[0][u1 * OBS + col];
-        else if (col == OBS) out = &G[1][u1];
-    } else if (e < PT::HW) {
-        out = &G[3][e - PT::B2];
-    } else if (e < PT::HB) {
-        const int i = e - PT::HW, a = i / 64, u = i % 64;
-        if (tw == 0) out = &dst.p[8][a * 64 + u];
-        else if (a == 0) out = &dst.p[10][u];
-    } else if (e < PT::LS) {
-        const int a = e - PT::HB;
-        if (tw == 0 && a < ACT) out = &dst.p[9][a];
-        else if (tw == 1 && a == 0) out = &dst.p[11][0];
-    } else if (e < PT::ST) {
-        const int a = e - PT::LS;
-        if (tw == 0 && a < ACT) {
-            out = &dst.p[12][a];
-            v -= ent_coef;  // d(ent_coef * -sum(0.5 + 0.5 log 2 pi + log_std))
-        }
-    } else if (stats) {
-        const int k = e - PT::ST;
-        const float inv_b = 1.0f / (float)bs;
-        if (tw == 0) {
-            if (k == 0) stats[0] = v * inv_b;  // policy_loss
-            if (k == 1) stats[3] = v * inv_b;  // clip_fraction
-            if (k == 2) stats[4] = v * inv_b;  // approx_kl
-            if (k == 3) {
-                float ent = 0.0f;
-                for (int a = 0; a < ACT; ++a) ent += 1.41893853320467274f + src.p[12][a];  // 0.5 + 0.5 log 2 pi
-                stats[2] = ent;  // entropy (per sample; the loss term is -ent)
-            }
-        } else if (k == 0) {
-            stats[1] = v * inv_b;  // value_loss
-        }
-    }
-    if (out) *out = v;
-    if (normw) {
-        float g2 = out ? v * v : 0.0f;
-#pragma unroll
-        for (int o = kFinElems / 2; o >= 1; o >>= 1) g2 += __shfl_xor(g2, o);
-        if (l == 0) {
-            normw[tw * gridDim.x + blockIdx.x] = g2;
-            if (tw == 0 && blockIdx.x == 0) normw[2 * gridDim.x] = *step0 + 1.0f;
-        }
-    }
+    constexpr bool CTL = false;
+    const ppo::CtlArgs ca = {};
+#include "rocket_ppo_finish_body.inc"
 }
 
 // clip_grad_norm_ + Adam step over a list of tensors (rr_clip_adam): the optimizer half of a
@@ -810,6 +775,17 @@ struct PpoLaunch {
 };
 static_assert(std::is_trivially_copyable_v<PpoLaunch>, "PpoLaunch crosses TUs by memcpy (rrc_launch_learner)");
 
+// rr_ppo_update_opts's launches (ppo_opts/rocket_ppo_opts.hip, rrc_launch_learner_opts): an
+// rr_ppo_update launch record (op 1) and the options
+struct PpoOptsLaunch {
+    PpoLaunch base;
+    const float* old_values;  // the value clip's rollout values (clip_vf > 0)
+    float clip_vf;            // <= 0: off
+    int normalize;            // normalize_advantage
+    ppo::CtlArgs ctl;
+};
+static_assert(std::is_trivially_copyable_v<PpoOptsLaunch>, "PpoOptsLaunch crosses TUs by memcpy");
+
 // Element k of policy tensor t (rr_ppo_grad order) into the packed images (two towers of Pack::SIZE).
 template <int OBS, int ACT>
 __device__ __forceinline__ void pack_scatter(float* __restrict__ pack, int t, int k, float v)
@@ -862,63 +838,7 @@ __global__ __launch_bounds__(kAdamThreads) void adam_chain_kernel(AdamList A, co
                                                                   float beta1, float beta2, float w1, float w2, float eps,
                                                                   float* __restrict__ pack, AdvNext nx, int nbp)
 {
-    if ((int)blockIdx.x >= nbp) {
-        __shared__ double red[2][kAdamThreads / kWave];
-        const int sub = threadIdx.x / 256, t = threadIdx.x % 256, b = (blockIdx.x - nbp) * 4 + sub;
-        double s = 0.0, q = 0.0;
-        ppo::adv_sums(nx.adv, nx.idx, nx.bs, (int64_t)b * 256 + t, s, q);
-        s = ppo::wave_sum(s);
-        q = ppo::wave_sum(q);
-        const int w = threadIdx.x / kWave;
-        if ((threadIdx.x & (kWave - 1)) == 0) {
-            red[0][w] = s;
-            red[1][w] = q;
-        }
-        __syncthreads();
-        if (t == 0) {
-            double ss = 0.0, qq = 0.0;
-            for (int k = 0; k < 256 / kWave; ++k) {
-                ss += red[0][sub * (256 / kWave) + k];
-                qq += red[1][sub * (256 / kWave) + k];
-            }
-            nx.part[2 * b] = ss;
-            nx.part[2 * b + 1] = qq;
-        }
-        return;
-    }
-    __shared__ float red[kAdamThreads / kWave];
-    // Every wave holds elements of one tensor (wstart: sizes rounded up to a wave), so the tensor
-    // and its pointers are scalar and the parameter scatter below branches per wave, not per lane.
-    // The element's four loads go first, unmasked (a padding lane reads element 0): their round
-    // trip overlaps the norm's.
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
-    const int64_t wbase = (int64_t)blockIdx.x * kAdamThreads + (int64_t)wv * kWave;
-    int t = 0;
-    while (t + 1 < A.n && wbase >= A.wstart[t + 1]) ++t;
-    const int64_t kw = wbase - A.wstart[t] + (threadIdx.x & (kWave - 1));
-    const bool live = wbase < A.wstart[A.n] && kw < A.start[t + 1] - A.start[t];
-    const int64_t k = live ? kw : 0;
-    const float g0 = A.grad[t][k], m0 = A.exp_avg[t][k], v0 = A.exp_avg_sq[t][k], p0 = A.param[t][k];
-    float part = 0.0f;
-    for (int b = threadIdx.x; b < n_norm; b += kAdamThreads) part += normw[b];
-    const float tot = block_sum<kAdamThreads>(part, red);
-    const float step = normw[n_norm], lr = *lr_p;
-    const float coef = max_norm > 0.0f ? fminf(max_norm / (sqrtf(tot) + 1e-6f), 1.0f) : 1.0f;
-    const float bc1 = 1.0f - powf(beta1, step), bc2 = 1.0f - powf(beta2, step);
-    const float sneg = -(1.0f / (bc1 / lr));
-    const float d = sqrtf(bc2) * sneg, eos = 1.0f / (sneg / eps);
-    if (live) {
-        const float g = g0 * coef;
-        A.grad[t][k] = g;
-        const float mk = m0 + w1 * (g - m0);
-        const float vk = v0 * beta2 + (w2 * g) * g;
-        A.exp_avg[t][k] = mk;
-        A.exp_avg_sq[t][k] = vk;
-        const float pk = p0 + mk / (sqrtf(vk) / d + eos);
-        A.param[t][k] = pk;
-        pack_scatter<OBS, ACT>(pack, t, (int)k, pk);
-    }
-    if (blockIdx.x == 0 && threadIdx.x < A.n) *A.step[threadIdx.x] = step;
+#include "rocket_ppo_adam_body.inc"
 }
 
 }  // namespace

@@ -655,6 +655,48 @@ class ClipAdam:
                    "rr_clip_adam")
 
 
+def _ppo_options(clip_range_vf, normalize_advantage, target_kl):
+    """SB3's three PPO.__init__ options as (clip_range_vf or 0.0, bool, target_kl or 0.0); None
+    switches the first and the last off, a number must be finite and > 0."""
+    out = []
+    for name, v in (("clip_range_vf", clip_range_vf), ("target_kl", target_kl)):
+        if v is None:
+            out.append(0.0)
+            continue
+        v = float(v)
+        if not (0.0 < v < float("inf")):
+            raise ValueError("%s must be None or a finite number > 0, not %r" % (name, v))
+        out.append(v)
+    return out[0], bool(normalize_advantage), out[1]
+
+
+def _old_values(ro, n):
+    v = getattr(ro, "values", None)
+    if v is None:
+        raise ValueError("clip_range_vf needs the rollout's values (ro.values)")
+    v = v.reshape(n)
+    if not v.is_contiguous() or v.dtype != torch.float32:
+        raise ValueError("rollout tensors must be contiguous fp32")
+    return v
+
+
+def _train_stats(ctl):
+    """SB3 PPO.train's log means from a control block read to the host (rocket_hip.h RR_PPO_CTL_*)."""
+    from . import _lib as L
+
+    n = max(ctl[L.RR_PPO_CTL_EVALS], 1.0)
+    stopped = ctl[L.RR_PPO_CTL_STOP] != 0.0
+    return {"train/policy_gradient_loss": ctl[L.RR_PPO_CTL_SUM_POLICY] / n,
+            "train/value_loss": ctl[L.RR_PPO_CTL_SUM_VALUE] / n,
+            "train/entropy_loss": -ctl[L.RR_PPO_CTL_SUM_ENTROPY] / n,
+            "train/clip_fraction": ctl[L.RR_PPO_CTL_SUM_CLIP] / n,
+            "train/approx_kl": ctl[L.RR_PPO_CTL_KL_SUM] / max(ctl[L.RR_PPO_CTL_KL_COUNT], 1.0),
+            "train/n_minibatches": int(ctl[L.RR_PPO_CTL_STEPS]),
+            "train/n_evaluated": int(ctl[L.RR_PPO_CTL_EVALS]),
+            "train/early_stop": bool(stopped),
+            "train/stop_epoch": int(ctl[L.RR_PPO_CTL_EPOCHS]) - 1 if stopped else None}
+
+
 class PPOUpdate(PPOGrad):
     """A whole PPO minibatch step — ``PPOGrad`` then ``ClipAdam``'s clip + Adam step on the same 13
     tensors — as ONE library call (``rr_ppo_update``). Without a gradient all_reduce between the
@@ -668,15 +710,29 @@ class PPOUpdate(PPOGrad):
       * The optimizer is the source of truth, as with ``ClipAdam``: its exp_avg / exp_avg_sq /
         step tensors are updated in place.
       * ``lr`` is read from a device scalar. ``sync_lr()`` refreshes it, and eager calls do so
-        themselves."""
+        themselves.
+
+    SB3's ``clip_range_vf``, ``normalize_advantage=False`` and ``target_kl`` (None / True / None:
+    today's ``rr_ppo_update`` calls, unchanged), or ``train_stats=True``, take the same step through
+    ``rr_ppo_update_opts``. That call carries a control block on the device (``self.ctl``):
+      * ``reset()`` clears it; call it before the first minibatch of a ``train()``-like pass and pass
+        ``epoch_start=True`` with every epoch's first minibatch.
+      * With ``target_kl``, the minibatch whose ``approx_kl > 1.5 target_kl`` takes no optimizer
+        step, and every later call is a no-op until ``reset()``. That is SB3's ``break``, without a
+        host read.
+      * ``train_stats()`` reads the block (one copy, which waits for the stream) and returns SB3's
+        ``train/*`` means over the pass."""
 
     def __init__(self, policy, optimizer, ro, batch_size, clip_range=0.2, ent_coef=0.01, vf_coef=0.5,
-                 max_grad_norm=0.5):
+                 max_grad_norm=0.5, clip_range_vf=None, normalize_advantage=True, target_kl=None, train_stats=False):
         import ctypes
 
         from . import _lib
 
         super().__init__(policy, ro, batch_size, clip_range, ent_coef, vf_coef)
+        cvf, norm, tkl = _ppo_options(clip_range_vf, normalize_advantage, target_kl)
+        self.opts = (_lib.RrPpoOptions(cvf, tkl, int(norm), int(bool(train_stats)))
+                     if cvf or tkl or not norm or train_stats else None)
         if not clip_adam_supported(optimizer, list(policy.parameters())):
             raise ValueError("PPOUpdate needs a capturable torch.optim.Adam over the policy's parameters "
                              "(one group, no weight decay / amsgrad / maximize)")
@@ -698,19 +754,37 @@ class PPOUpdate(PPOGrad):
         self.lr = torch.zeros(1, dtype=torch.float32, device=dev)
         self.sync_lr()
         nbytes = ctypes.c_int64()
-        _lib.check(self._lib.rr_ppo_update_workspace_size(self.ns, self.na, self.bs, ctypes.byref(nbytes)),
-                   "rr_ppo_update_workspace_size")
+        size = "rr_ppo_update_workspace_size" if self.opts is None else "rr_ppo_update_opts_workspace_size"
+        _lib.check(getattr(self._lib, size)(self.ns, self.na, self.bs, ctypes.byref(nbytes)), size)
         self.ws = torch.empty((nbytes.value + 15) // 16 * 4, dtype=torch.float32, device=dev)
         self._nbytes = nbytes.value
         self._next = None  # (address, rows) of the last call's next_idx: what chained=True may follow
+        self.ctl = self.old_values = None
+        if self.opts is not None:
+            self.ctl = torch.zeros(_lib.RR_PPO_CTL_SLOTS, dtype=torch.float32, device=dev)
+            if cvf:
+                self.old_values = _old_values(ro, self.data[0].shape[0])
+
+    def reset(self):
+        """Clear the control block (stream-ordered, no wait): a new ``train()`` pass begins."""
+        if self.ctl is None:
+            raise ValueError("this PPOUpdate has no control block (no option and no train_stats)")
+        self.ctl.zero_()
+
+    def train_stats(self):
+        if self.ctl is None:
+            raise ValueError("train_stats() needs PPOUpdate(train_stats=True) or one of the options")
+        return _train_stats(self.ctl.tolist())
 
     def sync_lr(self):
         self.lr.fill_(float(self.opt.param_groups[0]["lr"]))
 
-    def __call__(self, idx, next_idx=None, chained=False):
+    def __call__(self, idx, next_idx=None, chained=False, epoch_start=False):
         from . import _lib
 
         c = self._c
+        if epoch_start and self.opts is None:
+            raise ValueError("epoch_start belongs to the control block (no option and no train_stats here)")
         for t in (idx,) if next_idx is None else (idx, next_idx):
             if (t.dtype != torch.int64 or not 2 <= t.numel() <= self.bs or not t.is_contiguous()
                     or t.device != self.ws.device):
@@ -730,6 +804,18 @@ class PPOUpdate(PPOGrad):
         clip, ent, vf = self.coef
         o, a, lp, adv, ret = self.data
         nxt = None if next_idx is None else next_idx.data_ptr()
+        if self.opts is not None:
+            flags = (_lib.RR_PPO_CHAINED if chained else 0) | (_lib.RR_PPO_EPOCH_START if epoch_start else 0)
+            _lib.check(self._lib.rr_ppo_update_opts(
+                self.ns, self.na, self._params_w, self._dst, self._m, self._v, self._s, o.data_ptr(), a.data_ptr(),
+                lp.data_ptr(), adv.data_ptr(), ret.data_ptr(),
+                None if self.old_values is None else self.old_values.data_ptr(), idx.data_ptr(), idx.numel(), nxt,
+                0 if next_idx is None else next_idx.numel(), clip, ent, vf, self.max_norm, self.lr.data_ptr(),
+                float(b1), float(b2), float(grp["eps"]), c.byref(self.opts), self.ctl.data_ptr(),
+                self.stats.data_ptr(), flags, self.ws.data_ptr(), self._nbytes,
+                c.c_void_p(torch.cuda.current_stream(self.ws.device).cuda_stream)), "rr_ppo_update_opts")
+            self._next = None if next_idx is None else (next_idx.data_ptr(), next_idx.numel())
+            return self.stats
         _lib.check(self._lib.rr_ppo_update(
             self.ns, self.na, self._params_w, self._dst, self._m, self._v, self._s, o.data_ptr(), a.data_ptr(),
             lp.data_ptr(), adv.data_ptr(), ret.data_ptr(), idx.data_ptr(), idx.numel(), nxt,
@@ -764,7 +850,8 @@ def _epoch_perms(n, n_epochs, dev, generator=None):
 
 
 def ppo_update(policy, optimizer, ro, n_epochs=10, batch_size=65536, clip_range=0.2, ent_coef=0.01,
-               vf_coef=0.5, max_grad_norm=0.5, generator=None, group=None, fused=False):
+               vf_coef=0.5, max_grad_norm=0.5, generator=None, group=None, fused=False, clip_range_vf=None,
+               normalize_advantage=True, target_kl=None):
     """SB3 1.6 PPO.train on the device-resident rollout (advantage normalisation per
     minibatch, clipped surrogate, unclipped value loss, entropy bonus, grad-norm clip).
     ent_coef 0.01 as main_6DOF.py:68.
@@ -778,8 +865,23 @@ def ppo_update(policy, optimizer, ro, n_epochs=10, batch_size=65536, clip_range=
 
     ``fused=True``: the loss + backward of every minibatch is ``PPOGrad`` (one HIP pipeline)
     instead of PyTorch autograd, and for a capturable Adam the clip + optimizer step is
-    ``ClipAdam`` (one launch) on the optimizer's own state; the all_reduce is unchanged."""
+    ``ClipAdam`` (one launch) on the optimizer's own state; the all_reduce is unchanged.
+
+    ``clip_range_vf`` / ``normalize_advantage`` / ``target_kl`` are SB3's (None / True / None: its
+    defaults, and this function's behaviour without them). The autograd path implements all three,
+    ``target_kl`` with SB3's ``break``. ``fused=True`` takes them on the one-replica path with a
+    capturable Adam (``PPOUpdate``: ``rr_ppo_update_opts``, the stop carried on the device) and
+    refuses them elsewhere. ``target_kl`` with a ``group`` is refused everywhere: every rank would
+    decide on its own minibatch's KL."""
     n = ro.n_steps * ro.env.num_envs
+    cvf, norm, tkl = _ppo_options(clip_range_vf, normalize_advantage, target_kl)
+    if tkl and group is not None:
+        raise ValueError("target_kl with a group is not supported: the ranks would stop at different minibatches")
+    if fused and (cvf or tkl or not norm) and (group is not None
+                                               or not clip_adam_supported(optimizer, list(policy.parameters()))):
+        raise ValueError("fused=True takes clip_range_vf / normalize_advantage=False / target_kl only on the "
+                         "one-replica path with a capturable torch.optim.Adam (rr_ppo_update_opts), not with a "
+                         "group or another optimizer")
     if fused:
         perms = _epoch_perms(n, n_epochs, ro.obs.device, generator)
         if n % min(batch_size, n) == 1:
@@ -791,11 +893,15 @@ def ppo_update(policy, optimizer, ro, n_epochs=10, batch_size=65536, clip_range=
         stats = None
         if group is None and clip_adam_supported(optimizer, params):
             # the whole minibatch step in one call, chained: each call sums the next one's statistics
-            step = PPOUpdate(policy, optimizer, ro, min(batch_size, n), clip_range, ent_coef, vf_coef, max_grad_norm)
+            step = PPOUpdate(policy, optimizer, ro, min(batch_size, n), clip_range, ent_coef, vf_coef, max_grad_norm,
+                             clip_range_vf, normalize_advantage, target_kl)
+            kw = {}
             for perm in perms:
                 for s in range(0, n, step.bs):
                     nxt = perm[s + step.bs:s + 2 * step.bs] if s + step.bs < n else None
-                    stats = step(perm[s:s + step.bs], nxt, chained=s > 0)
+                    if step.opts is not None:
+                        kw = dict(epoch_start=s == 0)
+                    stats = step(perm[s:s + step.bs], nxt, chained=s > 0, **kw)
             return {} if stats is None else dict(zip(("policy_loss", "value_loss", "entropy"), stats[:3].tolist()))
         grad = PPOGrad(policy, ro, min(batch_size, n), clip_range, ent_coef, vf_coef)
         adam = ClipAdam(optimizer, params, max_grad_norm) if clip_adam_supported(optimizer, params) else None
@@ -815,20 +921,35 @@ def ppo_update(policy, optimizer, ro, n_epochs=10, batch_size=65536, clip_range=
     old_lp = ro.log_probs.reshape(n)
     adv_all = ro.advantages.reshape(n)
     ret = ro.returns.reshape(n)
+    old_v = ro.values.reshape(n) if cvf else None
     stats = {}
+    stop = False
     for _ in range(n_epochs):
+        if stop:
+            break
         perm = torch.randperm(n, device=obs.device, generator=generator)
         for s in range(0, n, batch_size):
             idx = perm[s:s + batch_size]
             mean, value = policy(obs[idx])
             lp = policy.log_prob(mean, act[idx])
             adv = adv_all[idx]
-            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+            if norm:
+                adv = (adv - adv.mean()) / (adv.std() + 1e-8)
             ratio = torch.exp(lp - old_lp[idx])
             pg = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - clip_range, 1 + clip_range)).mean()
+            if cvf:
+                value = old_v[idx] + torch.clamp(value - old_v[idx], -cvf, cvf)
             vf = torch.nn.functional.mse_loss(ret[idx], value)
             ent = -policy.entropy(len(idx)).mean()
             loss = pg + ent_coef * ent + vf_coef * vf
+            if tkl:
+                with torch.no_grad():
+                    log_ratio = lp - old_lp[idx]
+                    kl = float(((torch.exp(log_ratio) - 1) - log_ratio).mean())
+                if kl > 1.5 * tkl:  # SB3: the minibatch's losses are logged, its step is not taken
+                    stats = {"policy_loss": pg.detach(), "value_loss": vf.detach(), "entropy": -ent.detach()}
+                    stop = True
+                    break
             optimizer.zero_grad(set_to_none=True)
             loss.backward()
             if group is not None:
@@ -859,12 +980,26 @@ class GraphedPPOUpdate:
     and optimizer state restored in place), so the first ``update`` starts from the same state
     as the eager ``ppo_update`` would, and computes the same minibatch steps (``fused=False``: same
     kernels, same order; ``tests/test_gpu_rollout.py``). Multi-GPU: ``group`` must be an RCCL ("nccl") group —
-    the all_reduce is captured with the rest."""
+    the all_reduce is captured with the rest.
+
+    ``clip_range_vf`` / ``normalize_advantage`` / ``target_kl`` / ``train_stats`` (SB3's defaults and
+    False: exactly the calls described above) put the fused one-replica path on
+    ``rr_ppo_update_opts`` (``PPOUpdate``). ``update`` then clears the control block, every epoch's
+    first minibatch is captured with the epoch-start flag, and a KL stop needs no host decision: the
+    epochs after it replay as no-ops, and ``update`` still never waits for the device on their
+    account. ``train_stats()`` returns SB3's ``train/*`` means over the last ``update`` with one
+    copy. ``fused=False`` captures ``clip_range_vf`` and ``normalize_advantage`` as PyTorch ops and
+    refuses ``target_kl`` (a ``break`` cannot be captured); the split multi-GPU path refuses all."""
 
     def __init__(self, policy, optimizer, ro, batch_size=65536, clip_range=0.2, ent_coef=0.01, vf_coef=0.5,
-                 max_grad_norm=0.5, group=None, fused=None):
+                 max_grad_norm=0.5, group=None, fused=None, clip_range_vf=None, normalize_advantage=True,
+                 target_kl=None, train_stats=False):
         if not all(g.get("capturable", False) for g in optimizer.param_groups):
             raise ValueError("GraphedPPOUpdate needs an optimizer with capturable=True")
+        cvf, norm, tkl = _ppo_options(clip_range_vf, normalize_advantage, target_kl)
+        self._opt = (cvf, norm, tkl)
+        if tkl and group is not None:
+            raise ValueError("target_kl with a group is not supported: the ranks would stop at different minibatches")
         n = ro.n_steps * ro.env.num_envs
         if n % batch_size:
             raise ValueError("n_steps * num_envs (%d) must be a multiple of batch_size (%d)" % (n, batch_size))
@@ -900,9 +1035,17 @@ class GraphedPPOUpdate:
         if fused is None:
             fused = fused_grad_supported(policy, ro.env.state_dim, ro.env.action_dim)
         self.fused = bool(fused)
-        # fused, one replica, capturable Adam: the chained whole-minibatch call (rr_ppo_update)
-        self._update = (PPOUpdate(policy, optimizer, ro, batch_size, clip_range, ent_coef, vf_coef, max_grad_norm)
-                        if self.fused and group is None and clip_adam_supported(optimizer, params) else None)
+        one_call = self.fused and group is None and clip_adam_supported(optimizer, params)
+        if not one_call and (train_stats or tkl or (self.fused and (cvf or not norm))):
+            raise ValueError("clip_range_vf / normalize_advantage=False on the fused path, target_kl and train_stats "
+                             "need the fused one-replica update with a capturable torch.optim.Adam "
+                             "(rr_ppo_update_opts); fused=False takes clip_range_vf and normalize_advantage only")
+        self.old_v = _old_values(ro, n) if cvf and not self.fused else None
+        # fused, one replica, capturable Adam: the chained whole-minibatch call (rr_ppo_update, or
+        # rr_ppo_update_opts with an option or train_stats)
+        self._update = (PPOUpdate(policy, optimizer, ro, batch_size, clip_range, ent_coef, vf_coef, max_grad_norm,
+                                  clip_range_vf, normalize_advantage, target_kl, train_stats)
+                        if one_call else None)
         self._grad = (PPOGrad(policy, ro, batch_size, clip_range, ent_coef, vf_coef)
                       if self.fused and self._update is None else None)
         self._adam = (ClipAdam(optimizer, params, max_grad_norm)
@@ -931,6 +1074,8 @@ class GraphedPPOUpdate:
                             v.copy_(old[k])
                         else:
                             v.zero_()  # state the warm-up created: back to a fresh optimizer's
+        if self._update is not None and self._update.opts is not None:
+            self._update.reset()  # what the warm-up and the capture's eager side counted
         torch.cuda.synchronize(dev)
 
     def _mb(self, k):
@@ -940,7 +1085,8 @@ class GraphedPPOUpdate:
         clip_range, ent_coef, vf_coef, max_grad_norm = self.coef
         pol = self.policy
         if self._update is not None:
-            st = self._update(i, self._mb(k + 1) if k + 1 < self.n_mb else None, chained=k > 0)
+            kw = dict(epoch_start=k == 0) if self._update.opts is not None else {}
+            st = self._update(i, self._mb(k + 1) if k + 1 < self.n_mb else None, chained=k > 0, **kw)
             self._more = (st[3], st[4])
             return {"policy_loss": st[0], "value_loss": st[1], "entropy": st[2]}
         if self.fused:
@@ -954,12 +1100,16 @@ class GraphedPPOUpdate:
                 torch.nn.utils.clip_grad_norm_(self.params, max_grad_norm)
                 self.optimizer.step()
             return {"policy_loss": st[0], "value_loss": st[1], "entropy": st[2]}
+        cvf, norm, _ = self._opt
         mean, value = pol(self.obs[i])
         lp = pol.log_prob(mean, self.act[i])
         adv = self.adv_all[i]
-        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+        if norm:
+            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
         ratio = torch.exp(lp - self.old_lp[i])
         pg = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - clip_range, 1 + clip_range)).mean()
+        if cvf:
+            value = self.old_v[i] + torch.clamp(value - self.old_v[i], -cvf, cvf)
         vf = torch.nn.functional.mse_loss(self.ret[i], value)
         ent = -pol.entropy(self.bs).mean()
         loss = pg + ent_coef * ent + vf_coef * vf
@@ -981,6 +1131,17 @@ class GraphedPPOUpdate:
         out = {"train/" + k: float(v) for k, v in self.stats.items()}
         out["train/clip_fraction"], out["train/approx_kl"] = (float(v) for v in self._more)
         return out
+
+    def train_stats(self):
+        """SB3 PPO.train's log figures over the last ``update``, from the control block with one copy:
+        ``train/policy_gradient_loss``, ``train/value_loss``, ``train/entropy_loss``,
+        ``train/clip_fraction`` (means over every evaluated minibatch), ``train/approx_kl`` (mean
+        over the last, possibly partial, epoch), ``train/n_minibatches`` (optimizer steps applied),
+        ``train/n_evaluated``, ``train/early_stop`` and ``train/stop_epoch`` (None without a stop)."""
+        if self._update is None or self._update.opts is None:
+            raise ValueError("train_stats() needs GraphedPPOUpdate(train_stats=True) or one of the options on the "
+                             "fused one-replica path")
+        return self._update.train_stats()
 
     def _perm_streams(self):
         dev = self.obs.device
@@ -1012,6 +1173,8 @@ class GraphedPPOUpdate:
         for o in (self._adam, self._update):
             if o is not None:
                 o.sync_lr()  # the graph reads lr from the device: follow param_groups[0]["lr"]
+        if self._update is not None and self._update.opts is not None:
+            self._update.reset()  # a new train() pass: stop state and running sums cleared, stream-ordered
         main, bufs, side = self._perm_streams()
         ready, self._first = self._first, None
         if ready is None:  # no prepare(): the first epoch's draw in line
