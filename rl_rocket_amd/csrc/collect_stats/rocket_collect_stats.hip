@@ -3,10 +3,12 @@
 // rollout_stats_reduce_kernel, rocket_collect_stats.inc: rr_rollout_collect_stats), launched through
 // rrc_launch_collect_stats with the launch record of rrc_launch_collect (rocket_device.h: EnvLaunch)
 // and the same dispatcher. Compiled with the collect translation unit's settings (build.py
-// COLLECT_FLAGS, RR_POL_PREFETCH_A 1), because its loop is the collect's.
+// COLLECT_FLAGS, RR_POL_PREFETCH_A 1), because its loop is the collect's: both kernels include
+// rocket_rollout_body.inc.
 //
-// It is a translation unit of its own so that the kernels which existed before it keep their
-// machine code (see eval_trace/rocket_eval_trace.hip).
+// Sharing the body's text does not make one module of the two: this stays a translation unit of its
+// own so that the kernels which existed before it keep their machine code (see
+// eval_trace/rocket_eval_trace.hip).
 #include "rocket_device.h"
 // layer-2 A fragments read a group ahead, as in rocket_collect.hip (see rocket_policy.inc)
 #define RR_POL_PREFETCH_A 1

@@ -1,6 +1,7 @@
 // rocket_eval_trace.hip — the fourth translation unit of librocket_hip.so: the recording
-// evaluation kernels (eval_trace_kernel, rocket_eval.inc: rr_policy_evaluate_trace, the loop of
-// eval_kernel that also writes the histories of the envs with a trace slot), launched through
+// evaluation kernels (eval_trace_kernel, rocket_eval.inc: rr_policy_evaluate_trace, the body of
+// eval_kernel, rocket_eval_body.inc, with the regions that write the histories of the envs with a
+// trace slot), launched through
 // rrc_launch_eval_trace with the launch record of rrc_launch_eval (rocket_device.h: EnvLaunch) and
 // the same dispatcher. Compiled with the collect translation unit's settings (build.py
 // COLLECT_FLAGS, RR_POL_PREFETCH_A 1), because its loop is the collect's and eval_kernel's.

@@ -1422,6 +1422,23 @@ RolloutIO rollout_io(float* buf_obs, float* buf_action, float* buf_value, float*
     io.terms = terms;
     return io;
 }
+
+// what a whole rollout in one launch adds to them (rr_rollout_collect, rr_rollout_collect_stats):
+// the step count, the GAE coefficients and the end-of-rollout outputs
+void collect_io(RolloutIO& io, int n_steps, double gamma, double gae_lambda, float* buf_advantage, float* buf_return,
+                float* last_value, float* last_done, float* last_start)
+{
+    io.buf_adv = buf_advantage;
+    io.buf_ret = buf_return;
+    io.last_value = last_value;
+    io.last_done = last_done;
+    io.last_start = last_start;
+    io.t = 0;
+    io.T = (uint32_t)n_steps;
+    io.gamma = (float)gamma;  // the timeout bootstrap, fp32 as rr_rollout_step's
+    io.gamma64 = gamma;
+    io.lam = gae_lambda;
+}
 }  // namespace
 
 int rr_rollout_step(rr_env* e, const float* params, int precision, uint64_t seed, const uint64_t* iter, int t,
@@ -1451,16 +1468,7 @@ int rr_rollout_collect(rr_env* e, const float* params, int precision, uint64_t s
         return fail(RR_EINVAL, "rr_rollout_collect: buf_advantage and buf_return go together");
     RolloutIO io = rollout_io(buf_obs, buf_action, buf_value, buf_log_prob, buf_start, buf_reward, obs, reward, done,
                               truncated, terms);
-    io.buf_adv = buf_advantage;
-    io.buf_ret = buf_return;
-    io.last_value = last_value;
-    io.last_done = last_done;
-    io.last_start = last_start;
-    io.t = 0;
-    io.T = (uint32_t)n_steps;
-    io.gamma = (float)gamma;  // the timeout bootstrap, fp32 as rr_rollout_step's
-    io.gamma64 = gamma;
-    io.lam = gae_lambda;
+    collect_io(io, n_steps, gamma, gae_lambda, buf_advantage, buf_return, last_value, last_done, last_start);
     return launch_rollout(e, "rr_rollout_collect", true, params, precision, seed, iter, io, stream);
 }
 
@@ -1489,16 +1497,7 @@ int rr_rollout_collect_stats(rr_env* e, const float* params, int precision, uint
         return fail(RR_EINVAL, w + "the handle needs RR_FLAG_AUTO_RESET (episodes follow one another)");
     RolloutIO io = rollout_io(buf_obs, buf_action, buf_value, buf_log_prob, buf_start, buf_reward, obs, reward, done,
                               truncated, terms);
-    io.buf_adv = buf_advantage;
-    io.buf_ret = buf_return;
-    io.last_value = last_value;
-    io.last_done = last_done;
-    io.last_start = last_start;
-    io.t = 0;
-    io.T = (uint32_t)n_steps;
-    io.gamma = (float)gamma;  // as rr_rollout_collect
-    io.gamma64 = gamma;
-    io.lam = gae_lambda;
+    collect_io(io, n_steps, gamma, gae_lambda, buf_advantage, buf_return, last_value, last_done, last_start);
     const CollectStatsIO sio = {(uint64_t*)stats->partials, (uint64_t*)stats->out, (uint64_t*)stats->accum,
                                 (uint32_t)rr_rollout_stats_rows(e->n)};
     return launch_rollout(e, who, true, params, precision, seed, iter, io, stream, &sio);

@@ -621,10 +621,15 @@ __device__ __forceinline__ void bootstrap_wave(const float* sp, float* so2, cons
 // runs in fp64 and rounds each stored advantage / return once: terminal rewards of +-60 take |A|
 // past 128, where an fp32 scan's roundings add up to ~5e-5 over 16 steps (gamma, lambda as doubles
 // for the same reason: 0.99f is 0.99 + 9.5e-9).
-__device__ __forceinline__ void gae_env(int64_t T, int64_t n, int64_t e, const float* __restrict__ rewards,
-                                        const float* __restrict__ values, const float* __restrict__ starts,
-                                        float last_value, float last_done, double gamma, double lam,
-                                        float* __restrict__ adv, float* __restrict__ ret)
+// STATS (the statistics collect, rocket_rollout_body.inc) also sums over the env's samples y =
+// (double)ret[t], d = y - (double)value[t] into s: sum y, y^2, d, d^2, SB3 explained_variance's
+// inputs. s is an array reference, not a pointer: a `double* s = nullptr` parameter changed the
+// machine code of the kernels that take the sums. Without STATS s is not touched.
+template <bool STATS>
+__device__ __forceinline__ void gae_env_scan(int64_t T, int64_t n, int64_t e, const float* __restrict__ rewards,
+                                             const float* __restrict__ values, const float* __restrict__ starts,
+                                             float last_value, float last_done, double gamma, double lam,
+                                             float* __restrict__ adv, float* __restrict__ ret, double (&s)[4])
 {
     // backward over t in chunks of kC steps whose loads are all issued before the chunk's scan:
     // one memory round trip per chunk instead of one per step (the loads cannot move above the
@@ -653,12 +658,28 @@ __device__ __forceinline__ void gae_env(int64_t T, int64_t n, int64_t e, const f
                 const double v = vl[j];
                 last = fma(next_gl, last, fma(next_g, next_v, (double)rw[j] - v));
                 adv[k] = (float)last;
-                ret[k] = (float)(last + v);
+                const float rt = (float)(last + v);
+                ret[k] = rt;
                 next_v = v;
                 next_g = st[j] != 0.0f ? 0.0 : gamma;
                 next_gl = st[j] != 0.0f ? 0.0 : gl;
+                if constexpr (STATS) {
+                    const double y = (double)rt, d = y - v;
+                    s[0] += y;
+                    s[1] += y * y;
+                    s[2] += d;
+                    s[3] += d * d;
+                }
             }
     }
+}
+__device__ __forceinline__ void gae_env(int64_t T, int64_t n, int64_t e, const float* __restrict__ rewards,
+                                        const float* __restrict__ values, const float* __restrict__ starts,
+                                        float last_value, float last_done, double gamma, double lam,
+                                        float* __restrict__ adv, float* __restrict__ ret)
+{
+    double none[4];  // never read or written
+    gae_env_scan<false>(T, n, e, rewards, values, starts, last_value, last_done, gamma, lam, adv, ret, none);
 }
 
 }  // namespace pol
