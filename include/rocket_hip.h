@@ -676,6 +676,42 @@ int rr_ppo_update_opts(int obs_dim, int act_dim, float* const* params, float* co
                        float* control, float* stats, uint32_t flags, void* workspace, int64_t workspace_bytes,
                        void* stream);
 
+/* One behaviour-cloning minibatch step on demonstrations obs [M][obs_dim], actions [M][act_dim]
+ * (fp32, device), rows idx[0 .. batch): what imitation's bc.BC does per minibatch for SB3's
+ * MlpPolicy with a diagonal Gaussian, loss.backward() and Adam's step, without gradient clipping:
+ *   logp_i  = sum_a (-(actions_ia - mean_ia)^2 / (2 std_a^2) - log_std_a - 0.5 log 2 pi)
+ *   neglogp = -mean_i logp_i,   entropy = sum_a (0.5 + 0.5 log 2 pi + log_std_a)
+ *   l2_norm = 0.5 * sum over all 13 tensors of sum(w^2)
+ *   loss    = neglogp - ent_weight entropy + l2_weight l2_norm,   prob_true_act = mean_i exp(logp_i)
+ * The value tower and head receive the gradient l2_weight w only (zeros at l2_weight 0, written, and
+ * all 13 step tensors advance, as torch.optim.Adam does). Arrays, pointer conventions and the tensor
+ * order are rr_ppo_update's; stats is a device block of RR_BC_STAT_SLOTS floats or NULL.
+ * A call packs the pi tower's image, computes the gradient, finishes and runs Adam, which also
+ * refreshes the packed images: four launches. With flags & RR_BC_CHAINED the packing launch is
+ * skipped and the image the previous rr_bc_update left in the same workspace is used (nothing else
+ * may have written the parameters since; the batch may be smaller than the previous call's, on a
+ * workspace sized for the largest). Capturable in a graph; deterministic (fixed-order sums, no
+ * atomics); lr is a device float. RR_EINVAL before any launch for unsupported dimensions,
+ * batch < 2, a null argument or tensor, a workspace too small or not 16-B aligned, NaN or negative
+ * ent_weight / l2_weight, unknown flag bits. workspace: rr_bc_update_workspace_size bytes. */
+#define RR_BC_CHAINED 0x1u
+enum {
+    RR_BC_STAT_NEGLOGP = 0,
+    RR_BC_STAT_ENTROPY,
+    RR_BC_STAT_ENT_LOSS,       /* -ent_weight entropy */
+    RR_BC_STAT_PROB_TRUE_ACT,
+    RR_BC_STAT_L2_NORM,
+    RR_BC_STAT_L2_LOSS,        /* l2_weight l2_norm */
+    RR_BC_STAT_LOSS,
+    RR_BC_STAT_SLOTS = 8       /* floats */
+};
+int rr_bc_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes);
+int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* exp_avg,
+                 float* const* exp_avg_sq, float* const* step, const float* obs, const float* actions,
+                 const int64_t* idx, int64_t batch, float ent_weight, float l2_weight, const float* lr,
+                 double beta1, double beta2, float eps, float* stats, uint32_t flags,
+                 void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -129,6 +129,11 @@ RR_PPO_CHAINED, RR_PPO_EPOCH_START = 0x1, 0x2
  RR_PPO_CTL_SUM_VALUE, RR_PPO_CTL_SUM_ENTROPY, RR_PPO_CTL_SUM_CLIP, RR_PPO_CTL_KL_SUM, RR_PPO_CTL_KL_COUNT,
  RR_PPO_CTL_KL_LAST) = range(12)
 RR_PPO_CTL_SLOTS = 16
+# rr_bc_update's flag and the slots of its statistics block (rocket_hip.h RR_BC_STAT_*): 8 floats
+RR_BC_CHAINED = 0x1
+(RR_BC_STAT_NEGLOGP, RR_BC_STAT_ENTROPY, RR_BC_STAT_ENT_LOSS, RR_BC_STAT_PROB_TRUE_ACT, RR_BC_STAT_L2_NORM,
+ RR_BC_STAT_L2_LOSS, RR_BC_STAT_LOSS) = range(7)
+RR_BC_STAT_SLOTS = 8
 
 
 class RrEvalTrace(ctypes.Structure):
@@ -213,6 +218,10 @@ SIGNATURES = {
                            [ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                             ctypes.c_float, _P, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                             ctypes.POINTER(RrPpoOptions), _P, _P, ctypes.c_uint32, _P, ctypes.c_int64, _P]),
+    "rr_bc_update_workspace_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P]),
+    "rr_bc_update": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 8 +
+                     [ctypes.c_int64, ctypes.c_float, ctypes.c_float, _P, ctypes.c_double, ctypes.c_double,
+                      ctypes.c_float, _P, ctypes.c_uint32, _P, ctypes.c_int64, _P]),
 }
 
 _LIB = None

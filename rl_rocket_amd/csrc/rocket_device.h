@@ -1215,4 +1215,6 @@ __attribute__((visibility("hidden"))) int rrc_launch_eval_trace(const void* laun
 __attribute__((visibility("hidden"))) int rrc_launch_collect_stats(const void* launch, const void* io, const void* stats);
 __attribute__((visibility("hidden"))) int rrc_launch_learner(const void* launch, void* stream);
 __attribute__((visibility("hidden"))) int rrc_launch_learner_opts(const void* launch, void* stream);
+// bc/rocket_bc.hip: rr_bc_update's launches, a BcLaunch
+__attribute__((visibility("hidden"))) int rrc_launch_bc(const void* launch, void* stream);
 }

@@ -379,6 +379,7 @@ __attribute__((weak)) int rrc_launch_eval_trace(const void*, const void*, const 
 __attribute__((weak)) int rrc_launch_collect_stats(const void*, const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_learner(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_learner_opts(const void*, void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_bc(const void*, void*) { return kNoUnit; }
 }
 
 namespace {
@@ -1896,6 +1897,90 @@ int rr_ppo_update_opts(int obs_dim, int act_dim, float* const* params, float* co
     if (!stats) O.base.stats = (float*)((char*)workspace + upd);
     const hipError_t err = (hipError_t)rrc_launch_learner_opts(&O, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_opts: launch");
+}
+
+namespace {
+// rr_bc_update's workspace: 2 packed tower images | the finish's per-block sums and the step count,
+// 16-B rows | nwg partial-gradient vectors. What a call leaves for the chained one (the images) sits
+// ahead of the only section whose size follows the batch, as in ppo_carve.
+int64_t bc_fixed_floats(int obs_dim, int act_dim)
+{
+    const int64_t fin = (ppo_part_floats(obs_dim, act_dim) + kFinElems - 1) / kFinElems;
+    return 2 * ppo_pack_floats(obs_dim, act_dim) + (2 * fin + 1 + 3) / 4 * 4;
+}
+}  // namespace
+
+int rr_bc_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
+{
+    const int64_t pf = ppo_part_floats(obs_dim, act_dim);
+    if (!pf) return fail(RR_EINVAL, "rr_bc_update_workspace_size: supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
+    if (batch < 2 || !bytes) return fail(RR_EINVAL, "rr_bc_update_workspace_size: batch >= 2 and bytes required");
+    *bytes = (bc_fixed_floats(obs_dim, act_dim) + ppo_nwg(batch) * pf) * (int64_t)sizeof(float);
+#if defined(RR_DIAG_STAMPS)
+    // the shared gradient body writes its stamps past two towers' partial vectors: 16 floats per wave
+    *bytes += ppo_nwg(batch) * (pf + ppo::kWaves * 16) * (int64_t)sizeof(float);
+#endif
+    return RR_OK;
+}
+
+int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* exp_avg,
+                 float* const* exp_avg_sq, float* const* step, const float* obs, const float* actions,
+                 const int64_t* idx, int64_t batch, float ent_weight, float l2_weight, const float* lr,
+                 double beta1, double beta2, float eps, float* stats, uint32_t flags,
+                 void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (!ppo_part_floats(obs_dim, act_dim))
+        return fail(RR_EINVAL, "rr_bc_update: supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
+    if (batch < 2) return fail(RR_EINVAL, "rr_bc_update: batch >= 2 required");
+    int64_t need = 0;
+    rr_bc_update_workspace_size(obs_dim, act_dim, batch, &need);
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !obs || !actions || !idx || !lr || !workspace)
+        return fail(RR_EINVAL, "rr_bc_update: null argument");
+    if (workspace_bytes < need) return fail(RR_EINVAL, "rr_bc_update: workspace smaller than rr_bc_update_workspace_size");
+    if (((uintptr_t)workspace & 15) != 0) return fail(RR_EINVAL, "rr_bc_update: workspace must be 16-B aligned");
+    // NaN fails the comparison too
+    if (!(ent_weight >= 0.0f)) return fail(RR_EINVAL, "rr_bc_update: ent_weight must be >= 0");
+    if (!(l2_weight >= 0.0f)) return fail(RR_EINVAL, "rr_bc_update: l2_weight must be >= 0");
+    if (flags & ~RR_BC_CHAINED) return fail(RR_EINVAL, "rr_bc_update: unknown flag bits");
+    const int na = act_dim, no = obs_dim;
+    const int64_t numel[13] = {64 * no, 64, 64 * 64, 64, 64 * no, 64, 64 * 64, 64, 64 * na, na, 64, 1, na};
+    BcLaunch L = {};
+    L.a.n = 13;
+    for (int k = 0; k < 13; ++k) {
+        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || !step[k])
+            return fail(RR_EINVAL, "rr_bc_update: null parameter, gradient or optimizer-state tensor");
+        L.ps.p[k] = params[k];
+        L.pg.p[k] = grads[k];
+        L.a.param[k] = params[k];
+        L.a.grad[k] = grads[k];
+        L.a.exp_avg[k] = exp_avg[k];
+        L.a.exp_avg_sq[k] = exp_avg_sq[k];
+        L.a.step[k] = step[k];
+        L.a.start[k + 1] = L.a.start[k] + numel[k];
+        L.a.wstart[k + 1] = L.a.wstart[k] + (numel[k] + kWave - 1) / kWave * kWave;
+    }
+    L.obs_dim = obs_dim;
+    L.nwg = (int)ppo_nwg(batch);
+    L.pack = (float*)workspace;
+    L.normw = L.pack + 2 * ppo_pack_floats(obs_dim, act_dim);
+    L.part = L.pack + bc_fixed_floats(obs_dim, act_dim);
+    L.nbp = (int)((L.a.wstart[13] + kAdamThreads - 1) / kAdamThreads);
+    L.obs = obs;
+    L.actions = actions;
+    L.idx = idx;
+    L.batch = batch;
+    L.ent = ent_weight;
+    L.l2 = l2_weight;
+    L.lr = lr;
+    L.beta1 = (float)beta1;
+    L.beta2 = (float)beta2;
+    L.w1 = (float)(1.0 - beta1);
+    L.w2 = (float)(1.0 - beta2);
+    L.eps = eps;
+    L.stats = stats;
+    L.flags = flags;
+    const hipError_t err = (hipError_t)rrc_launch_bc(&L, stream);
+    return err == hipSuccess ? RR_OK : hip_fail(err, "rr_bc_update: launch");
 }
 
 

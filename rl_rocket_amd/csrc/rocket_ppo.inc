@@ -43,6 +43,8 @@
 // rr_ppo_update_opts (CTL: stop word, running statistics). ppo_opts/rocket_ppo_opts.hip instantiates
 // them with the options on, in kernels of its own: ppo_prep_body and ppo_grad_tower as functions,
 // the finish and optimizer bodies as included text (rocket_ppo_finish_body.inc).
+// bc/rocket_bc.hip (rr_bc_update, behaviour cloning) instantiates the pi tower with LOSS 1 and
+// includes the same two bodies.
 #pragma once
 
 #include <type_traits>
@@ -272,7 +274,10 @@ __global__ __launch_bounds__(256) void ppo_prep_kernel(const float* __restrict__
 //   dV = vf_coef 2 (Vc - ret) / B where -clip_vf <= V - old <= clip_vf (torch's clamp passes the
 //   gradient on the closed interval), else 0.
 // NORM false (normalize_advantage=False): A = adv[idx], the minibatch statistics are not read.
-template <int OBS, int ACT, int TW, bool VCLIP = false, bool NORM = true>
+// LOSS 1 (behaviour cloning, bc/rocket_bc.hip; pi tower, NORM false): loss = -mean(log_prob(a)), so
+// d loss / d log_prob = -1 / B for every sample: no ratio, no clip; old_lp / adv are not read, and
+// the three sums are -log_prob, exp(log_prob) and a spare.
+template <int OBS, int ACT, int TW, bool VCLIP = false, bool NORM = true, int LOSS = 0>
 __device__ __forceinline__ void ppo_grad_tower(
     float* __restrict__ lds, const float* __restrict__ obs, const float* __restrict__ act,
     const float* __restrict__ old_lp, const float* __restrict__ adv, const float* __restrict__ ret,
@@ -318,8 +323,10 @@ __device__ __forceinline__ void ppo_grad_tower(
         if (tw == 0) {
 #pragma unroll
             for (int a = 0; a < ACT; ++a) in.a[a] = act[r * ACT + a];
-            in.olp = old_lp[r];
-            in.av = adv[r];
+            if constexpr (LOSS == 0) {
+                in.olp = old_lp[r];
+                in.av = adv[r];
+            }
         } else {
             in.av = ret[r];
             if constexpr (VCLIP) in.olp = old_val[r];  // with the tile's other rows: unmasked, one tile ahead
@@ -419,7 +426,8 @@ __device__ __forceinline__ void ppo_grad_tower(
         float dh[ACT];
         if (tw == 0) {
             float A;
-            if constexpr (NORM) A = valid ? ((in.av - a_mean) - a_mean_lo) / a_den : 0.0f;
+            if constexpr (LOSS == 1) A = 0.0f;  // no advantages
+            else if constexpr (NORM) A = valid ? ((in.av - a_mean) - a_mean_lo) / a_den : 0.0f;
             else A = valid ? in.av : 0.0f;
             float lp = 0.0f, d[ACT];
 #pragma unroll
@@ -428,14 +436,20 @@ __device__ __forceinline__ void ppo_grad_tower(
                 d[a] = in.a[a] - mean;
                 lp += -(d[a] * d[a]) / var[a] - ls[a] - 0.918938533204672742f;
             }
-            const float lr = lp - in.olp;
-            const float r = expf(lr);
-            const float cr = fminf(fmaxf(r, lo), hi);
-            const float u = A * r, c = A * cr;
-            const float gu = u < c ? 1.0f : (u == c ? 0.5f : 0.0f);
-            const float gc = c < u ? 1.0f : (u == c ? 0.5f : 0.0f);
-            const float mask = (r >= lo && r <= hi) ? 1.0f : 0.0f;
-            const float dlp = valid ? -inv_b * (A * gu + A * gc * mask) * r : 0.0f;
+            // d loss / d lp; PPO's ratio terms are read again by its sums below
+            float dlp, lr, r, u, c;
+            if constexpr (LOSS == 1) {
+                dlp = valid ? -inv_b : 0.0f;
+            } else {
+                lr = lp - in.olp;
+                r = expf(lr);
+                const float cr = fminf(fmaxf(r, lo), hi);
+                u = A * r, c = A * cr;
+                const float gu = u < c ? 1.0f : (u == c ? 0.5f : 0.0f);
+                const float gc = c < u ? 1.0f : (u == c ? 0.5f : 0.0f);
+                const float mask = (r >= lo && r <= hi) ? 1.0f : 0.0f;
+                dlp = valid ? -inv_b * (A * gu + A * gc * mask) * r : 0.0f;
+            }
 #pragma unroll
             for (int a = 0; a < ACT; ++a) {
                 // d lp / d mean = 2 d / (2 std^2); d lp / d log_std = d^2 / std^2 - 1
@@ -446,9 +460,14 @@ __device__ __forceinline__ void ppo_grad_tower(
                 }
             }
             if (half == 0 && valid) {
-                st0 -= fminf(u, c);
-                st1 += fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
-                st2 += (r - 1.0f) - lr;
+                if constexpr (LOSS == 1) {
+                    st0 -= lp;
+                    st1 += expf(lp);
+                } else {
+                    st0 -= fminf(u, c);
+                    st1 += fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
+                    st2 += (r - 1.0f) - lr;
+                }
             }
         } else {
             const float v = pol::head_dot<1>(sp + K::HW, h2, 0, half) + sp[K::HB];
@@ -785,6 +804,23 @@ struct PpoOptsLaunch {
     ppo::CtlArgs ctl;
 };
 static_assert(std::is_trivially_copyable_v<PpoOptsLaunch>, "PpoOptsLaunch crosses TUs by memcpy");
+
+// rr_bc_update's launches (bc/rocket_bc.hip, rrc_launch_bc): pack the pi image, the pi tower's
+// gradient on nwg workgroups, the finish over both halves and the statistics, Adam with the repack
+struct BcLaunch {
+    PolSrc ps;
+    PolGrad pg;
+    AdamList a;
+    const float *obs, *actions, *lr;
+    const int64_t* idx;
+    int64_t batch;
+    float ent, l2, beta1, beta2, w1, w2, eps;
+    float* stats;  // 8 floats (RR_BC_STAT_*) or null
+    float *part, *pack, *normw;
+    int obs_dim, nwg, nbp;
+    uint32_t flags;
+};
+static_assert(std::is_trivially_copyable_v<BcLaunch>, "BcLaunch crosses TUs by memcpy");
 
 // Element k of policy tensor t (rr_ppo_grad order) into the packed images (two towers of Pack::SIZE).
 template <int OBS, int ACT>

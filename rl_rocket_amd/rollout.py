@@ -1517,3 +1517,6 @@ def evaluate_policy(policy, batch, n_eval_episodes=5, return_episode_rewards=Fal
         return res.ep_return.cpu()[m].tolist(), res.ep_length.cpu()[m].tolist()
     s = res.stats()
     return s["mean_reward"], s["std_reward"]
+
+
+from .bc import BCUpdate, Demonstrations, bc_train  # noqa: E402,F401  (behaviour cloning, beside PPOUpdate)
