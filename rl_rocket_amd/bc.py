@@ -22,6 +22,11 @@ import math
 import numpy as np
 import torch
 
+from . import _lib
+from .learner import (_AdamState, _allreduce_grads, _check_idx, _check_params, _epoch_perms, _stream, _workspace,
+                      clip_adam_supported)
+from .policy import _policy_tensors, fused_grad_supported
+
 STAT_NAMES = ("neglogp", "entropy", "ent_loss", "prob_true_act", "l2_norm", "l2_loss", "loss")  # RR_BC_STAT_*
 
 
@@ -108,7 +113,7 @@ def _bc_loss(policy, obs, acts, ent_weight, l2_weight):
     return loss, (neglogp, entropy, ent_loss, logp.exp().mean(), l2_norm, l2_loss, loss)
 
 
-class BCUpdate:
+class BCUpdate(_AdamState):
     """One behaviour-cloning minibatch step as ONE library call (``rr_bc_update``): the loss of this
     module's head and its backward on fp32 MFMA, then ``torch.optim.Adam``'s capturable step on the
     optimizer's own state tensors, without gradient clipping. Four launches, three when chained.
@@ -124,11 +129,6 @@ class BCUpdate:
     ``last_stats()`` returns the seven figures as a dict (one copy, which waits for the stream)."""
 
     def __init__(self, policy, optimizer, demos, batch_size, ent_weight=1e-3, l2_weight=0.0):
-        import ctypes
-
-        from . import _lib
-        from .rollout import _policy_tensors, clip_adam_supported, fused_grad_supported
-
         ns, na = demos.obs.shape[1], demos.acts.shape[1]
         if not fused_grad_supported(policy, ns, na):
             raise ValueError("BCUpdate needs an MlpActorCritic with 64x64 towers and (obs, act) in ((14, 3), (7, 2))")
@@ -140,71 +140,31 @@ class BCUpdate:
         if not clip_adam_supported(optimizer, list(policy.parameters())):
             raise ValueError("BCUpdate needs a capturable torch.optim.Adam over the policy's parameters "
                              "(one group, no weight decay / amsgrad / maximize)")
-        self._lib, self._c = _lib.load(), ctypes
+        self._lib = _lib.load()
         self.ns, self.na, self.bs = ns, na, int(batch_size)
         self.ent_weight, self.l2_weight = float(ent_weight), float(l2_weight)
-        self.demos, self.opt = demos, optimizer
+        self.demos = demos
         dev = demos.device
         self.params = _policy_tensors(policy)
-        for p in self.params:
-            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
-                raise ValueError("rr_bc_update needs contiguous fp32 parameters on the demonstrations' device")
-            if p.grad is None:
-                p.grad = torch.zeros_like(p)
-            st = optimizer.state[p]
-            if not st:
-                st["step"] = torch.zeros((), dtype=torch.float32, device=dev)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            if not st["step"].is_cuda or st["step"].dtype != torch.float32:
-                raise ValueError("BCUpdate needs the capturable Adam's device float32 step tensors")
-        self._grads = [p.grad for p in self.params]
-        self._state = [(optimizer.state[p]["exp_avg"], optimizer.state[p]["exp_avg_sq"], optimizer.state[p]["step"])
-                       for p in self.params]
-        P = ctypes.c_void_p * 13
-        self._params_w = P(*[p.data_ptr() for p in self.params])
-        self._dst = P(*[g.data_ptr() for g in self._grads])
-        self._m, self._v, self._s = (P(*[st[k].data_ptr() for st in self._state]) for k in range(3))
-        self.lr = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.sync_lr()
-        nbytes = ctypes.c_int64()
-        _lib.check(self._lib.rr_bc_update_workspace_size(ns, na, self.bs, ctypes.byref(nbytes)),
-                   "rr_bc_update_workspace_size")
-        self.ws = torch.empty((nbytes.value + 15) // 16 * 4, dtype=torch.float32, device=dev)
-        self._nbytes = nbytes.value
+        _check_params("rr_bc_update", self.params, dev, "demonstrations'")
+        self._bind_adam(optimizer, self.params)
+        self.ws, self._nbytes = _workspace(self._lib, "rr_bc_update_workspace_size", dev, ns, na, self.bs)
         self.stats = torch.zeros(_lib.RR_BC_STAT_SLOTS, dtype=torch.float32, device=dev)
         self._versions = None  # the parameters' version counters after the last call: what chained=True may follow
-
-    def sync_lr(self):
-        self.lr.fill_(float(self.opt.param_groups[0]["lr"]))
 
     def last_stats(self):
         return dict(zip(STAT_NAMES, self.stats.tolist()))
 
     def __call__(self, idx, chained=False):
-        from . import _lib
-
-        c = self._c
-        if (idx.dtype != torch.int64 or idx.dim() != 1 or not 2 <= idx.numel() <= self.bs or not idx.is_contiguous()
-                or idx.device != self.ws.device):
-            raise ValueError("idx must be a contiguous int64 device tensor of 2 .. batch_size rows")
+        _check_idx(idx, self.bs, self.ws.device, flat=True)
         if chained and self._versions != [p._version for p in self.params]:
             raise ValueError("chained=True needs the previous call on this BCUpdate to be the last writer of the "
                              "parameters")
-        for p, g, (m, v, s) in zip(self.params, self._grads, self._state):
-            st = self.opt.state[p]
-            if p.grad is not g or st["exp_avg"] is not m or st["exp_avg_sq"] is not v or st["step"] is not s:
-                raise RuntimeError("a gradient or Adam state tensor was replaced; BCUpdate holds their addresses")
-        if not torch.cuda.is_current_stream_capturing():
-            self.sync_lr()
-        grp = self.opt.param_groups[0]
-        b1, b2 = grp["betas"]
         _lib.check(self._lib.rr_bc_update(
-            self.ns, self.na, self._params_w, self._dst, self._m, self._v, self._s, self.demos.obs.data_ptr(),
-            self.demos.acts.data_ptr(), idx.data_ptr(), idx.numel(), self.ent_weight, self.l2_weight,
-            self.lr.data_ptr(), float(b1), float(b2), float(grp["eps"]), self.stats.data_ptr(),
-            _lib.RR_BC_CHAINED if chained else 0, self.ws.data_ptr(), self._nbytes,
-            c.c_void_p(torch.cuda.current_stream(self.ws.device).cuda_stream)), "rr_bc_update")
+            self.ns, self.na, *self._ptrs, self.demos.obs.data_ptr(), self.demos.acts.data_ptr(), idx.data_ptr(),
+            idx.numel(), self.ent_weight, self.l2_weight, *self._adam_args(), self.stats.data_ptr(),
+            _lib.RR_BC_CHAINED if chained else 0, self.ws.data_ptr(), self._nbytes, _stream(self.ws.device)),
+            "rr_bc_update")
         self._versions = [p._version for p in self.params]
         return self.stats
 
@@ -223,8 +183,6 @@ def bc_train(policy, optimizer, demos, n_epochs=1, batch_size=None, generator=No
     insists, ``fused=False`` is the autograd path. A ``torch.distributed`` ``group`` averages the
     minibatch gradients over the ranks on the autograd path; the fused call has no gradient-only half
     and refuses it."""
-    from .rollout import _allreduce_grads, _epoch_perms, clip_adam_supported, fused_grad_supported
-
     m = len(demos)
     bs = min(m, 65536) if batch_size is None else int(batch_size)
     if not 1 <= bs <= m:

@@ -1644,6 +1644,83 @@ void ppo_carve(PpoLaunch& L, int obs_dim, int act_dim, int64_t batch, void* work
     L.pack = (float*)((char*)workspace + 2 * ppo::kAdvPart * sizeof(double));
     L.part = L.pack + 2 * ppo_pack_floats(obs_dim, act_dim);
 }
+
+// rr_bc_update's workspace: 2 packed tower images | the finish's per-block sums and the step count,
+// 16-B rows | nwg partial-gradient vectors. What a call leaves for the chained one (the images) sits
+// ahead of the only section whose size follows the batch, as in ppo_carve.
+int64_t bc_fixed_floats(int obs_dim, int act_dim)
+{
+    const int64_t fin = (ppo_part_floats(obs_dim, act_dim) + kFinElems - 1) / kFinElems;
+    return 2 * ppo_pack_floats(obs_dim, act_dim) + (2 * fin + 1 + 3) / 4 * 4;
+}
+
+// What the learner entry points share. `who` names the entry point in the error text, built only on a refusal.
+int refuse(const char* who, const std::string& what) { return fail(RR_EINVAL, std::string(who) + ": " + what); }
+
+// The shape checks of the four *_workspace_size calls (sized: `bytes` is required too) and of rr_bc_update
+int learner_shape_ok(const char* who, int obs_dim, int act_dim, int64_t batch, const int64_t* bytes, bool sized = true)
+{
+    if (!ppo_part_floats(obs_dim, act_dim)) return refuse(who, "supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
+    if (batch < 2 || (sized && !bytes)) return refuse(who, sized ? "batch >= 2 and bytes required" : "batch >= 2 required");
+    return RR_OK;
+}
+
+// rr_ppo_workspace_size's bytes for a shape that passed: ppo_carve's three sections
+int64_t ppo_bytes(int obs_dim, int act_dim, int64_t batch)
+{
+    const int64_t floats = ppo_nwg(batch) * ppo_part_floats(obs_dim, act_dim) + ppo_pack_floats(obs_dim, act_dim);
+    return (int64_t)(2 * ppo::kAdvPart * sizeof(double)) + 2 * floats * (int64_t)sizeof(float);
+}
+
+// rr_ppo_update_workspace_size's: + the finish kernel's squared-gradient sums (two towers) and the step count, 16-B rows
+int64_t ppo_update_bytes(int obs_dim, int act_dim, int64_t batch)
+{
+    const int64_t fin = (ppo_part_floats(obs_dim, act_dim) + kFinElems - 1) / kFinElems;
+    return (ppo_bytes(obs_dim, act_dim, batch) + 15) / 16 * 16 + (2 * fin + 1 + 3) / 4 * 16;
+}
+
+// The 13 policy tensors (rr_policy_pack order) into a launch record; false if one is null. With `a` also the
+// optimizer launch's list: each tensor's Adam state and the prefix sums of the sizes (params are then writable)
+bool bind_policy(PolSrc& ps, PolGrad& pg, AdamList* a, int no, int na, const float* const* params, float* const* grads,
+                 float* const* exp_avg = nullptr, float* const* exp_avg_sq = nullptr, float* const* step = nullptr)
+{
+    const int64_t numel[13] = {64 * no, 64, 64 * 64, 64, 64 * no, 64, 64 * 64, 64, 64 * na, na, 64, 1, na};
+    if (a) a->n = 13;
+    for (int k = 0; k < 13; ++k) {
+        if (!params[k] || !grads[k] || (a && (!exp_avg[k] || !exp_avg_sq[k] || !step[k]))) return false;
+        ps.p[k] = params[k];
+        pg.p[k] = grads[k];
+        if (!a) continue;
+        a->param[k] = const_cast<float*>(params[k]);
+        a->grad[k] = grads[k];
+        a->exp_avg[k] = exp_avg[k];
+        a->exp_avg_sq[k] = exp_avg_sq[k];
+        a->step[k] = step[k];
+        a->start[k + 1] = a->start[k] + numel[k];
+        a->wstart[k + 1] = a->wstart[k] + (numel[k] + kWave - 1) / kWave * kWave;
+    }
+    return true;
+}
+
+// Adam's hyper-parameters into a PpoLaunch or a BcLaunch (a generic lambda: no template inside extern "C")
+const auto set_adam = [](auto& L, const float* lr, double beta1, double beta2, float eps) {
+    L.lr = lr;
+    L.beta1 = (float)beta1;
+    L.beta2 = (float)beta2;
+    L.w1 = (float)(1.0 - beta1);
+    L.w2 = (float)(1.0 - beta2);
+    L.eps = eps;
+};
+
+// The workspace and flag checks of rr_ppo_update, rr_ppo_update_opts and rr_bc_update
+int learner_ws_ok(const char* who, const void* workspace, int64_t bytes, int64_t need, uint32_t flags, uint32_t known_flags)
+{
+    if (!workspace) return refuse(who, "null argument");
+    if (bytes < need) return refuse(who, std::string("workspace smaller than ") + who + "_workspace_size");
+    if (((uintptr_t)workspace & 15) != 0) return refuse(who, "workspace must be 16-B aligned");
+    if (flags & ~known_flags) return refuse(who, "unknown flag bits");
+    return RR_OK;
+}
 }  // namespace
 
 int rr_clip_adam_workspace_size(int64_t total_elements, int64_t* bytes)
@@ -1681,25 +1758,16 @@ int rr_clip_adam(int n_tensors, float* const* params, float* const* grads, float
     L.a = a;
     L.work = (float*)workspace;
     L.max_norm = max_grad_norm;
-    L.lr = lr;
-    L.beta1 = (float)beta1;
-    L.beta2 = (float)beta2;
-    L.w1 = (float)(1.0 - beta1);
-    L.w2 = (float)(1.0 - beta2);
-    L.eps = eps;
+    set_adam(L, lr, beta1, beta2, eps);
     const hipError_t err = (hipError_t)rrc_launch_learner(&L, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_clip_adam: launch");
 }
 
 int rr_ppo_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
 {
-    const int64_t pf = ppo_part_floats(obs_dim, act_dim);
-    if (!pf) return fail(RR_EINVAL, "rr_ppo_workspace_size: supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
-    if (batch < 2 || !bytes) return fail(RR_EINVAL, "rr_ppo_workspace_size: batch >= 2 and bytes required");
-    // adv partial sums | 2 packed tower images | 2 towers x nwg partial-gradient vectors
-    *bytes = (int64_t)(2 * ppo::kAdvPart * sizeof(double)) +
-             2 * (ppo_nwg(batch) * pf + ppo_pack_floats(obs_dim, act_dim)) * (int64_t)sizeof(float);
-    return RR_OK;
+    const int rc = learner_shape_ok("rr_ppo_workspace_size", obs_dim, act_dim, batch, bytes);
+    if (rc == RR_OK) *bytes = ppo_bytes(obs_dim, act_dim, batch);
+    return rc;
 }
 
 int rr_ppo_grad(int obs_dim, int act_dim, const float* const* params, float* const* grads, const float* obs,
@@ -1708,8 +1776,7 @@ int rr_ppo_grad(int obs_dim, int act_dim, const float* const* params, float* con
                 void* workspace, int64_t workspace_bytes, void* stream)
 {
     int64_t need = 0;
-    const int rc = rr_ppo_workspace_size(obs_dim, act_dim, batch, &need);
-    if (rc != RR_OK) return rc;
+    if (const int rc = rr_ppo_workspace_size(obs_dim, act_dim, batch, &need); rc != RR_OK) return rc;
     if (!params || !grads || !obs || !actions || !old_log_prob || !advantages || !returns || !idx || !workspace)
         return fail(RR_EINVAL, "rr_ppo_grad: null argument");
     if (workspace_bytes < need) return fail(RR_EINVAL, "rr_ppo_grad: workspace smaller than rr_ppo_workspace_size");
@@ -1717,11 +1784,8 @@ int rr_ppo_grad(int obs_dim, int act_dim, const float* const* params, float* con
     if (!(clip_range >= 0.0f)) return fail(RR_EINVAL, "rr_ppo_grad: clip_range must be >= 0");
     PpoLaunch L = {};
     L.op = 0;
-    for (int k = 0; k < 13; ++k) {
-        if (!params[k] || !grads[k]) return fail(RR_EINVAL, "rr_ppo_grad: null parameter or gradient tensor");
-        L.ps.p[k] = params[k];
-        L.pg.p[k] = grads[k];
-    }
+    if (!bind_policy(L.ps, L.pg, nullptr, obs_dim, act_dim, params, grads))
+        return fail(RR_EINVAL, "rr_ppo_grad: null parameter or gradient tensor");
     ppo_carve(L, obs_dim, act_dim, batch, workspace);
     L.obs = obs;
     L.actions = actions;
@@ -1740,15 +1804,9 @@ int rr_ppo_grad(int obs_dim, int act_dim, const float* const* params, float* con
 
 int rr_ppo_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
 {
-    int64_t ppo = 0;
-    if (!ppo_part_floats(obs_dim, act_dim))
-        return fail(RR_EINVAL, "rr_ppo_update_workspace_size: supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
-    if (batch < 2 || !bytes) return fail(RR_EINVAL, "rr_ppo_update_workspace_size: batch >= 2 and bytes required");
-    rr_ppo_workspace_size(obs_dim, act_dim, batch, &ppo);
-    // + the finish kernel's squared-gradient sums (two towers) and the step count, 16-B rows
-    const int64_t fin = (ppo_part_floats(obs_dim, act_dim) + kFinElems - 1) / kFinElems;
-    *bytes = (ppo + 15) / 16 * 16 + (2 * fin + 1 + 3) / 4 * 16;
-    return RR_OK;
+    const int rc = learner_shape_ok("rr_ppo_update_workspace_size", obs_dim, act_dim, batch, bytes);
+    if (rc == RR_OK) *bytes = ppo_update_bytes(obs_dim, act_dim, batch);
+    return rc;
 }
 
 namespace {
@@ -1762,38 +1820,19 @@ int ppo_update_record(const char* who, PpoLaunch& L, int obs_dim, int act_dim, f
                       const float* lr, double beta1, double beta2, float eps, float* stats, uint32_t flags,
                       uint32_t known_flags, void* workspace, int64_t workspace_bytes, int64_t ws_need)
 {
-    const std::string w = std::string(who) + ": ";
-    int64_t ppo_bytes = 0;
-    rr_ppo_workspace_size(obs_dim, act_dim, batch, &ppo_bytes);
     if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !obs || !actions || !old_log_prob || !advantages ||
-        !returns || !idx || !lr || !workspace)
-        return fail(RR_EINVAL, (w + "null argument").c_str());
-    if (workspace_bytes < ws_need) return fail(RR_EINVAL, (w + "workspace smaller than " + who + "_workspace_size").c_str());
-    if (((uintptr_t)workspace & 15) != 0) return fail(RR_EINVAL, (w + "workspace must be 16-B aligned").c_str());
-    if (!(clip_range >= 0.0f)) return fail(RR_EINVAL, (w + "clip_range must be >= 0").c_str());
-    if (flags & ~known_flags) return fail(RR_EINVAL, (w + "unknown flag bits").c_str());
-    if (next_idx && !(next_batch >= 2 && next_batch <= batch))
-        return fail(RR_EINVAL, (w + "next_batch must be in [2, batch]").c_str());
-    const int na = act_dim, no = obs_dim;
-    const int64_t numel[13] = {64 * no, 64, 64 * 64, 64, 64 * no, 64, 64 * 64, 64, 64 * na, na, 64, 1, na};
+        !returns || !idx || !lr)
+        return refuse(who, "null argument");
+    const int rc = learner_ws_ok(who, workspace, workspace_bytes, ws_need, flags, known_flags);
+    if (rc != RR_OK) return rc;
+    if (!(clip_range >= 0.0f)) return refuse(who, "clip_range must be >= 0");
+    if (next_idx && !(next_batch >= 2 && next_batch <= batch)) return refuse(who, "next_batch must be in [2, batch]");
     L = {};
     L.op = 1;
-    L.a.n = 13;
-    for (int k = 0; k < 13; ++k) {
-        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || !step[k])
-            return fail(RR_EINVAL, (w + "null parameter, gradient or optimizer-state tensor").c_str());
-        L.ps.p[k] = params[k];
-        L.pg.p[k] = grads[k];
-        L.a.param[k] = params[k];
-        L.a.grad[k] = grads[k];
-        L.a.exp_avg[k] = exp_avg[k];
-        L.a.exp_avg_sq[k] = exp_avg_sq[k];
-        L.a.step[k] = step[k];
-        L.a.start[k + 1] = L.a.start[k] + numel[k];
-        L.a.wstart[k + 1] = L.a.wstart[k] + (numel[k] + kWave - 1) / kWave * kWave;
-    }
+    if (!bind_policy(L.ps, L.pg, &L.a, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step))
+        return refuse(who, "null parameter, gradient or optimizer-state tensor");
     ppo_carve(L, obs_dim, act_dim, batch, workspace);
-    L.normw = (float*)((char*)workspace + (ppo_bytes + 15) / 16 * 16);
+    L.normw = (float*)((char*)workspace + (ppo_bytes(obs_dim, act_dim, batch) + 15) / 16 * 16);
     L.nbp = (int)((L.a.wstart[13] + kAdamThreads - 1) / kAdamThreads);
     L.obs = obs;
     L.actions = actions;
@@ -1808,12 +1847,7 @@ int ppo_update_record(const char* who, PpoLaunch& L, int obs_dim, int act_dim, f
     L.ent = ent_coef;
     L.vf = vf_coef;
     L.max_norm = max_grad_norm;
-    L.lr = lr;
-    L.beta1 = (float)beta1;
-    L.beta2 = (float)beta2;
-    L.w1 = (float)(1.0 - beta1);
-    L.w2 = (float)(1.0 - beta2);
-    L.eps = eps;
+    set_adam(L, lr, beta1, beta2, eps);
     L.stats = stats;
     L.flags = flags & RR_PPO_CHAINED;
     return RR_OK;
@@ -1828,13 +1862,12 @@ int rr_ppo_update(int obs_dim, int act_dim, float* const* params, float* const* 
                   float* stats, uint32_t flags, void* workspace, int64_t workspace_bytes, void* stream)
 {
     int64_t need = 0;
-    int rc = rr_ppo_update_workspace_size(obs_dim, act_dim, batch, &need);
-    if (rc != RR_OK) return rc;
+    if (const int rc = rr_ppo_update_workspace_size(obs_dim, act_dim, batch, &need); rc != RR_OK) return rc;
     PpoLaunch L;
-    rc = ppo_update_record("rr_ppo_update", L, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step, obs, actions,
-                           old_log_prob, advantages, returns, idx, batch, next_idx, next_batch, clip_range, ent_coef,
-                           vf_coef, max_grad_norm, lr, beta1, beta2, eps, stats, flags, RR_PPO_CHAINED, workspace,
-                           workspace_bytes, need);
+    const int rc = ppo_update_record("rr_ppo_update", L, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step, obs,
+                                     actions, old_log_prob, advantages, returns, idx, batch, next_idx, next_batch, clip_range,
+                                     ent_coef, vf_coef, max_grad_norm, lr, beta1, beta2, eps, stats, flags, RR_PPO_CHAINED,
+                                     workspace, workspace_bytes, need);
     if (rc != RR_OK) return rc;
     const hipError_t err = (hipError_t)rrc_launch_learner(&L, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update: launch");
@@ -1850,13 +1883,10 @@ static_assert(ppo::kStop == RR_PPO_CTL_STOP && ppo::kDecide == RR_PPO_CTL_DECIDE
 
 int rr_ppo_update_opts_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
 {
-    int64_t upd = 0;
-    if (!ppo_part_floats(obs_dim, act_dim))
-        return fail(RR_EINVAL, "rr_ppo_update_opts_workspace_size: supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
-    if (batch < 2 || !bytes) return fail(RR_EINVAL, "rr_ppo_update_opts_workspace_size: batch >= 2 and bytes required");
-    rr_ppo_update_workspace_size(obs_dim, act_dim, batch, &upd);
-    *bytes = upd + 32;  // + 8 floats: the call's statistics when the caller passes none (the control block sums them)
-    return RR_OK;
+    const int rc = learner_shape_ok("rr_ppo_update_opts_workspace_size", obs_dim, act_dim, batch, bytes);
+    // + 8 floats: the call's statistics when the caller passes none (the control block sums them)
+    if (rc == RR_OK) *bytes = ppo_update_bytes(obs_dim, act_dim, batch) + 32;
+    return rc;
 }
 
 int rr_ppo_update_opts(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* exp_avg,
@@ -1868,15 +1898,13 @@ int rr_ppo_update_opts(int obs_dim, int act_dim, float* const* params, float* co
                        float* control, float* stats, uint32_t flags, void* workspace, int64_t workspace_bytes,
                        void* stream)
 {
-    int64_t need = 0, upd = 0;
-    int rc = rr_ppo_update_opts_workspace_size(obs_dim, act_dim, batch, &need);
-    if (rc != RR_OK) return rc;
-    rr_ppo_update_workspace_size(obs_dim, act_dim, batch, &upd);
+    int64_t need = 0;
+    if (const int rc = rr_ppo_update_opts_workspace_size(obs_dim, act_dim, batch, &need); rc != RR_OK) return rc;
     PpoOptsLaunch O = {};
-    rc = ppo_update_record("rr_ppo_update_opts", O.base, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step, obs,
-                           actions, old_log_prob, advantages, returns, idx, batch, next_idx, next_batch, clip_range,
-                           ent_coef, vf_coef, max_grad_norm, lr, beta1, beta2, eps, stats, flags,
-                           RR_PPO_CHAINED | RR_PPO_EPOCH_START, workspace, workspace_bytes, need);
+    const int rc = ppo_update_record("rr_ppo_update_opts", O.base, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step,
+                                     obs, actions, old_log_prob, advantages, returns, idx, batch, next_idx, next_batch,
+                                     clip_range, ent_coef, vf_coef, max_grad_norm, lr, beta1, beta2, eps, stats, flags,
+                                     RR_PPO_CHAINED | RR_PPO_EPOCH_START, workspace, workspace_bytes, need);
     if (rc != RR_OK) return rc;
     if (!options) return fail(RR_EINVAL, "rr_ppo_update_opts: null options");
     // NaN fails both comparisons' complements: !(x >= 0) is true for NaN and for negatives
@@ -1894,27 +1922,15 @@ int rr_ppo_update_opts(int obs_dim, int act_dim, float* const* params, float* co
     O.ctl.ctl = control;
     O.ctl.kl_limit = options->target_kl > 0.0f ? 1.5f * options->target_kl : HUGE_VALF;
     O.ctl.epoch_start = (flags & RR_PPO_EPOCH_START) != 0;
-    if (!stats) O.base.stats = (float*)((char*)workspace + upd);
+    if (!stats) O.base.stats = (float*)((char*)workspace + ppo_update_bytes(obs_dim, act_dim, batch));
     const hipError_t err = (hipError_t)rrc_launch_learner_opts(&O, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_opts: launch");
 }
 
-namespace {
-// rr_bc_update's workspace: 2 packed tower images | the finish's per-block sums and the step count,
-// 16-B rows | nwg partial-gradient vectors. What a call leaves for the chained one (the images) sits
-// ahead of the only section whose size follows the batch, as in ppo_carve.
-int64_t bc_fixed_floats(int obs_dim, int act_dim)
-{
-    const int64_t fin = (ppo_part_floats(obs_dim, act_dim) + kFinElems - 1) / kFinElems;
-    return 2 * ppo_pack_floats(obs_dim, act_dim) + (2 * fin + 1 + 3) / 4 * 4;
-}
-}  // namespace
-
 int rr_bc_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
 {
+    if (const int rc = learner_shape_ok("rr_bc_update_workspace_size", obs_dim, act_dim, batch, bytes); rc != RR_OK) return rc;
     const int64_t pf = ppo_part_floats(obs_dim, act_dim);
-    if (!pf) return fail(RR_EINVAL, "rr_bc_update_workspace_size: supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
-    if (batch < 2 || !bytes) return fail(RR_EINVAL, "rr_bc_update_workspace_size: batch >= 2 and bytes required");
     *bytes = (bc_fixed_floats(obs_dim, act_dim) + ppo_nwg(batch) * pf) * (int64_t)sizeof(float);
 #if defined(RR_DIAG_STAMPS)
     // the shared gradient body writes its stamps past two towers' partial vectors: 16 floats per wave
@@ -1929,36 +1945,19 @@ int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* g
                  double beta1, double beta2, float eps, float* stats, uint32_t flags,
                  void* workspace, int64_t workspace_bytes, void* stream)
 {
-    if (!ppo_part_floats(obs_dim, act_dim))
-        return fail(RR_EINVAL, "rr_bc_update: supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
-    if (batch < 2) return fail(RR_EINVAL, "rr_bc_update: batch >= 2 required");
     int64_t need = 0;
+    if (const int rc = learner_shape_ok("rr_bc_update", obs_dim, act_dim, batch, nullptr, false); rc != RR_OK) return rc;
     rr_bc_update_workspace_size(obs_dim, act_dim, batch, &need);
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !obs || !actions || !idx || !lr || !workspace)
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !obs || !actions || !idx || !lr)
         return fail(RR_EINVAL, "rr_bc_update: null argument");
-    if (workspace_bytes < need) return fail(RR_EINVAL, "rr_bc_update: workspace smaller than rr_bc_update_workspace_size");
-    if (((uintptr_t)workspace & 15) != 0) return fail(RR_EINVAL, "rr_bc_update: workspace must be 16-B aligned");
+    const int rc = learner_ws_ok("rr_bc_update", workspace, workspace_bytes, need, flags, RR_BC_CHAINED);
+    if (rc != RR_OK) return rc;
     // NaN fails the comparison too
     if (!(ent_weight >= 0.0f)) return fail(RR_EINVAL, "rr_bc_update: ent_weight must be >= 0");
     if (!(l2_weight >= 0.0f)) return fail(RR_EINVAL, "rr_bc_update: l2_weight must be >= 0");
-    if (flags & ~RR_BC_CHAINED) return fail(RR_EINVAL, "rr_bc_update: unknown flag bits");
-    const int na = act_dim, no = obs_dim;
-    const int64_t numel[13] = {64 * no, 64, 64 * 64, 64, 64 * no, 64, 64 * 64, 64, 64 * na, na, 64, 1, na};
     BcLaunch L = {};
-    L.a.n = 13;
-    for (int k = 0; k < 13; ++k) {
-        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || !step[k])
-            return fail(RR_EINVAL, "rr_bc_update: null parameter, gradient or optimizer-state tensor");
-        L.ps.p[k] = params[k];
-        L.pg.p[k] = grads[k];
-        L.a.param[k] = params[k];
-        L.a.grad[k] = grads[k];
-        L.a.exp_avg[k] = exp_avg[k];
-        L.a.exp_avg_sq[k] = exp_avg_sq[k];
-        L.a.step[k] = step[k];
-        L.a.start[k + 1] = L.a.start[k] + numel[k];
-        L.a.wstart[k + 1] = L.a.wstart[k] + (numel[k] + kWave - 1) / kWave * kWave;
-    }
+    if (!bind_policy(L.ps, L.pg, &L.a, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step))
+        return fail(RR_EINVAL, "rr_bc_update: null parameter, gradient or optimizer-state tensor");
     L.obs_dim = obs_dim;
     L.nwg = (int)ppo_nwg(batch);
     L.pack = (float*)workspace;
@@ -1971,17 +1970,11 @@ int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* g
     L.batch = batch;
     L.ent = ent_weight;
     L.l2 = l2_weight;
-    L.lr = lr;
-    L.beta1 = (float)beta1;
-    L.beta2 = (float)beta2;
-    L.w1 = (float)(1.0 - beta1);
-    L.w2 = (float)(1.0 - beta2);
-    L.eps = eps;
+    set_adam(L, lr, beta1, beta2, eps);
     L.stats = stats;
     L.flags = flags;
     const hipError_t err = (hipError_t)rrc_launch_bc(&L, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_bc_update: launch");
 }
-
 
 }  // extern "C"

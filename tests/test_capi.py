@@ -224,3 +224,64 @@ def test_abi_8_to_12_entry_points_refuse_bad_arguments_before_any_hip_call():
     # rollouts / GAE (kept from ABI 3-7)
     refused(lib.rr_gae(16, 0, fake, fake, fake, fake, fake, ctypes.c_double(0.99), ctypes.c_double(0.95), fake, fake,
                        None), "rr_gae")
+
+
+# The parent commit's byte counts (read from its library, not from the code under test), per
+# (obs_dim, act_dim), at the edges of the learner's workgroup count: one workgroup per 128 rows,
+# capped at 128 workgroups.
+_WS_BATCHES = (2, 128, 129, 16384, 16385, 65536)
+_WS_BYTES = {
+    "rr_ppo_workspace_size": {(14, 3): (130720, 130720, 182016, 6645312, 6645312, 6645312),
+                              (7, 2): (126624, 126624, 177408, 6576192, 6576192, 6576192)},
+    "rr_ppo_update_workspace_size": {(14, 3): (132336, 132336, 183632, 6646928, 6646928, 6646928),
+                                     (7, 2): (128224, 128224, 179008, 6577792, 6577792, 6577792)},
+    "rr_ppo_update_opts_workspace_size": {(14, 3): (132368, 132368, 183664, 6646960, 6646960, 6646960),
+                                          (7, 2): (128256, 128256, 179040, 6577824, 6577824, 6577824)},
+    "rr_bc_update_workspace_size": {(14, 3): (102592, 102592, 128240, 3359888, 3359888, 3359888),
+                                    (7, 2): (98736, 98736, 124128, 3323520, 3323520, 3323520)},
+}
+
+
+def test_fused_learner_calls_refuse_bad_arguments_and_keep_their_workspace_sizes():
+    """rr_ppo_update, rr_ppo_update_opts and rr_bc_update share their argument checks: each refuses,
+    with RR_EINVAL and a message naming itself, a null at either end of each of its five 13-pointer
+    lists (index 12: the list is read to the end), a too-small or misaligned workspace, an unknown
+    flag bit, batch 1 and an unsupported shape. Fake pointers as above: nothing is dereferenced,
+    nothing launches. The four workspace sizes are the bytes the library returned before the checks
+    were merged."""
+    lib = _lib.load()
+    V = ctypes.c_void_p
+    fake, lr = V(0x10000), V(0x20000)
+    adam = (lr, 0.9, 0.999, 1e-5)
+    opts = _lib.RrPpoOptions(0.0, 0.0, 1, 0)
+
+    def ppo(lists, shape, batch, flags, wsp, ws_bytes):
+        return lib.rr_ppo_update(*shape, *lists, *[fake] * 6, batch, None, 0, 0.2, 0.01, 0.5, 0.5, *adam, None, flags,
+                                 wsp, ws_bytes, None)
+
+    def ppo_opts(lists, shape, batch, flags, wsp, ws_bytes):
+        return lib.rr_ppo_update_opts(*shape, *lists, *[fake] * 5, None, fake, batch, None, 0, 0.2, 0.01, 0.5, 0.5,
+                                      *adam, ctypes.byref(opts), None, None, flags, wsp, ws_bytes, None)
+
+    def bc(lists, shape, batch, flags, wsp, ws_bytes):
+        return lib.rr_bc_update(*shape, *lists, *[fake] * 3, batch, 1e-3, 0.0, *adam, None, flags, wsp, ws_bytes, None)
+
+    good = dict(shape=(14, 3), batch=64, flags=0, wsp=fake, ws_bytes=1 << 30)
+    bad = [dict(ws_bytes=16), dict(wsp=V(0x10008)), dict(flags=0x80), dict(batch=1), dict(shape=(9, 3))]
+    for name, call in (("rr_ppo_update", ppo), ("rr_ppo_update_opts", ppo_opts), ("rr_bc_update", bc)):
+        cases = [([_ptrs(13, null_at=at if k == which else None) for k in range(5)], good)
+                 for which in range(5) for at in (0, 12)]
+        cases += [([_ptrs(13) for _ in range(5)], {**good, **kw}) for kw in bad]
+        assert len(cases) == 15
+        for lists, kw in cases:
+            rc = call(lists, **kw)
+            assert rc == _lib.RR_EINVAL, (name, kw, rc)
+            assert name.encode() in lib.rr_last_error(), (name, kw, lib.rr_last_error())
+    ws = ctypes.c_int64()
+    for size, table in _WS_BYTES.items():
+        for shape, expected in table.items():
+            got = []
+            for batch in _WS_BATCHES:
+                assert getattr(lib, size)(*shape, batch, ctypes.byref(ws)) == 0, (size, shape, batch)
+                got.append(ws.value)
+            assert tuple(got) == expected, (size, shape, got)

@@ -376,3 +376,44 @@ def test_ppo_update_chain_carries_what_a_fresh_prep_computes(model):
     with pytest.raises(ValueError):
         upd[0](mbs[1], chained=True)  # the last call handed over no next minibatch
     env.close()
+
+
+@pytest.mark.parametrize("cls", ["ClipAdam", "PPOUpdate", "BCUpdate"])
+def test_fused_calls_refuse_a_replaced_gradient_or_adam_state_tensor(cls):
+    """The library is given the addresses of the gradients and of the optimizer's exp_avg / exp_avg_sq
+    / step tensors once. After a good call, each of the four replaced in turn on one parameter makes
+    the next call raise RuntimeError naming the class; with the tensor put back the call goes through
+    again. 7 observations / 2 actions, 64 envs x 4 steps, batch_size 64."""
+    import torch
+    from rl_rocket_amd.rollout import BCUpdate, ClipAdam, Demonstrations, PPOUpdate
+
+    env, pol, ro = _rollout_for_update(n=64, T=4, model=3)
+    opt = torch.optim.Adam(pol.parameters(), lr=3e-4, eps=1e-5, capturable=True)
+    idx = torch.randperm(256, device="cuda:0", generator=torch.Generator("cuda:0").manual_seed(3))[:64].contiguous()
+    if cls == "ClipAdam":
+        call = ClipAdam(opt, list(pol.parameters()), 0.5)
+    elif cls == "PPOUpdate":
+        step = PPOUpdate(pol, opt, ro, 64)
+        call = lambda: step(idx)  # noqa: E731
+    else:
+        step = BCUpdate(pol, opt, Demonstrations.from_rollout(ro), 64)
+        call = lambda: step(idx)  # noqa: E731
+    call()
+    p = pol.pi_net[2].weight
+    state = opt.state[p]
+    for key in ("grad", "exp_avg", "exp_avg_sq", "step"):
+        kept = p.grad if key == "grad" else state[key]
+        if key == "grad":
+            p.grad = kept.clone()
+        else:
+            state[key] = kept.clone()
+        with pytest.raises(RuntimeError, match="replaced; %s holds their addresses" % cls):
+            call()
+        if key == "grad":
+            p.grad = kept
+        else:
+            state[key] = kept
+    call()
+    torch.cuda.synchronize()
+    assert float(state["step"]) == 2.0
+    env.close()

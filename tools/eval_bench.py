@@ -19,7 +19,7 @@
   the exact mode's evaluation (rr_policy_evaluate_exact) against the step-by-step path on the same
   work: 6DOF, fp32 towers, the scaled test policy (tests/rollout_ref.py), one episode per env from a
   fresh reset under TimeLimit `--tl`. Two batches with the same seed, one evaluated with
-  PolicyEvaluator(fused=True), one with fused=False (rollout.py's _run_unfused: `--tl` iterations of
+  PolicyEvaluator(fused=True), one with fused=False (evaluate.py's _run_unfused: `--tl` iterations of
   a PyTorch policy forward, two exact steps and the state round trips), alternating, `--reps` timed
   runs each after a warm-up run, HIP events around run(). The record holds every run, the medians
   and spreads, env-steps per second, the ratio, and `--tl` x the committed rocprofv3 time of one
