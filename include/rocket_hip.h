@@ -712,6 +712,63 @@ int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* g
                  double beta1, double beta2, float eps, float* stats, uint32_t flags,
                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Discrete 3DOF actions: the Categorical policy --------------------------------------------------
+ * The reference's DiscreteActions3DOF (wrappers.py:24-35) turns the 3DOF env's [gimbal, thrust]
+ * action into Discrete(K) through a table of K rows; behind it SB3 builds an MlpPolicy with the same
+ * 64x64 towers, an action head of K logits and no log_std (stable_baselines3
+ * CategoricalDistribution: log_prob = logit_a - logsumexp(logits), entropy = -sum_k p_k log p_k,
+ * mode = argmax). obs_dim is 7, n_choices K is 2 .. 4. The policy has 12 tensors, rr_policy_pack's
+ * order without log_std: pi {W1, b1, W2, b2}, vf {W1, b1, W2, b2}, W_action [K][64], b_action [K],
+ * W_value [1][64], b_value. Kernels and packed images are those of a 4-head policy (the <7, 4>
+ * instantiation of the layouts); heads k >= K are packed as zeros, stay out of the softmax and
+ * receive no gradient. fp32 towers only.
+ *
+ * Packing: _discrete twins of rr_policy_layout / rr_policy_pack, because the source list has 12
+ * tensors and the head tensors K rows; rr_policy_layout / rr_policy_pack and their instantiations are
+ * untouched. rr_policy_layout_discrete returns the size in floats and the same 12 offsets (LS is
+ * four unused floats). rr_policy_bootstrap is reused: it accepts (obs_dim, act_dim) = (7, 4) with
+ * RR_POLICY_FP32 for an image packed by rr_policy_pack_discrete. */
+int rr_policy_layout_discrete(int obs_dim, int64_t* off);
+int rr_policy_pack_discrete(int obs_dim, int n_choices, const float* const* src, float* params, void* stream);
+
+/* rr_policy_act for this policy, one launch: value [n] and, per env i,
+ *   z_k = logit k (k < K), m = max z, p_k = exp(z_k - m) / sum, log p_k = (z_k - m) - log(sum)
+ *   u = (mix32(key) >> 8) 2^-24 in [0, 1), key being rr_policy_act's three mix32 rounds over
+ *       (env_id_offset + i, splitmix64(seed), *iter, t)
+ *   index = the number of k in 0 .. K - 2 with p_0 + .. + p_k <= u (fp32 running sum): inverse-CDF
+ *           sampling, always in 0 .. K - 1
+ *   action [n] = index as a float (SB3's [n_steps, n_envs, 1] buffer), log_prob [n] = log p_index,
+ *   action_env [n][2] = table[index] (the rr_step input).
+ * table is a HOST array [n_choices][2] of finite floats, copied into the launch. The other arguments,
+ * the previous step's bootstrap (reward_out) and the episode-start flags (start_out) are
+ * rr_policy_act's. RR_EINVAL before any launch for obs_dim != 7, n_choices outside 2 .. 4, a
+ * precision other than RR_POLICY_FP32, a non-finite table entry and what rr_policy_act refuses. */
+int rr_policy_act_discrete(const float* params, int obs_dim, int n_choices, const float* table, int precision,
+                           int64_t n, int64_t env_id_offset, const float* obs, uint64_t seed, const uint64_t* iter,
+                           int t, float* action_env, float* action, float* value, float* log_prob, float* obs_copy,
+                           const float* prev_term_obs, const uint8_t* prev_truncated, const float* prev_reward,
+                           float gamma, float* reward_out, const uint8_t* done, float* start_out, void* stream);
+
+/* rr_ppo_update for this policy: SB3 1.6 PPO.train's minibatch step with a Categorical distribution.
+ * Arguments are rr_ppo_update's with n_choices for act_dim; the five tensor lists have 12 entries
+ * (the order above); actions is [rows], the chosen index as a float. The loss is rr_ppo_grad's with
+ *   log_prob = log p_a,   entropy = mean_i H_i,  H = -sum_k p_k log p_k (0 for a term whose p_k is 0)
+ * so the entropy bonus is state dependent and its gradient is part of each sample's logit gradient
+ *   d loss / d z_k = dlp ((k == a) - p_k) + ent_coef / B p_k (log p_k + H).
+ * stats[5] as rr_ppo_grad's, stats[2] the mean entropy. RR_PPO_CHAINED, next_idx, the workspace rules,
+ * the clip and Adam arithmetic are rr_ppo_update's: four launches, three chained; capturable;
+ * deterministic (fixed-order sums, no atomics). RR_EINVAL before any launch for obs_dim != 7,
+ * n_choices outside 2 .. 4, batch < 2 and what rr_ppo_update refuses.
+ * workspace: rr_ppo_update_discrete_workspace_size bytes. */
+int rr_ppo_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes);
+int rr_ppo_update_discrete(int obs_dim, int n_choices, float* const* params, float* const* grads,
+                           float* const* exp_avg, float* const* exp_avg_sq, float* const* step, const float* obs,
+                           const float* actions, const float* old_log_prob, const float* advantages,
+                           const float* returns, const int64_t* idx, int64_t batch, const int64_t* next_idx,
+                           int64_t next_batch, float clip_range, float ent_coef, float vf_coef, float max_grad_norm,
+                           const float* lr, double beta1, double beta2, float eps, float* stats, uint32_t flags,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

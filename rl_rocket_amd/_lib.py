@@ -222,6 +222,16 @@ SIGNATURES = {
     "rr_bc_update": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 8 +
                      [ctypes.c_int64, ctypes.c_float, ctypes.c_float, _P, ctypes.c_double, ctypes.c_double,
                       ctypes.c_float, _P, ctypes.c_uint32, _P, ctypes.c_int64, _P]),
+    "rr_policy_layout_discrete": (ctypes.c_int, [ctypes.c_int, _P]),
+    "rr_policy_pack_discrete": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    "rr_policy_act_discrete": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int64,
+                                              ctypes.c_int64, _P, ctypes.c_uint64, _P, ctypes.c_int, _P, _P, _P, _P,
+                                              _P, _P, _P, _P, ctypes.c_float, _P, _P, _P, _P]),
+    "rr_ppo_update_discrete_workspace_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P]),
+    "rr_ppo_update_discrete": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 11 +
+                               [ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                ctypes.c_float, _P, ctypes.c_double, ctypes.c_double, ctypes.c_float, _P,
+                                ctypes.c_uint32, _P, ctypes.c_int64, _P]),
 }
 
 _LIB = None

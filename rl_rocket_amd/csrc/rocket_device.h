@@ -1217,4 +1217,6 @@ __attribute__((visibility("hidden"))) int rrc_launch_learner(const void* launch,
 __attribute__((visibility("hidden"))) int rrc_launch_learner_opts(const void* launch, void* stream);
 // bc/rocket_bc.hip: rr_bc_update's launches, a BcLaunch
 __attribute__((visibility("hidden"))) int rrc_launch_bc(const void* launch, void* stream);
+// discrete/rocket_discrete.hip: the Categorical policy's launches, a DiscreteLaunch
+__attribute__((visibility("hidden"))) int rrc_launch_discrete(const void* launch, void* stream);
 }

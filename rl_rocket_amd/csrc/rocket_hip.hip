@@ -380,6 +380,7 @@ __attribute__((weak)) int rrc_launch_collect_stats(const void*, const void*, con
 __attribute__((weak)) int rrc_launch_learner(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_learner_opts(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_bc(const void*, void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_discrete(const void*, void*) { return kNoUnit; }
 }
 
 namespace {
@@ -1345,6 +1346,23 @@ int rr_policy_bootstrap(const float* params, int obs_dim, int act_dim, int preci
     if (!term_obs && !value_out) return fail(RR_EINVAL, "rr_policy_bootstrap: nothing to do");
     if (value_out && !obs) return fail(RR_EINVAL, "rr_policy_bootstrap: value_out needs obs");
     if (((uintptr_t)params & 15) != 0) return fail(RR_EINVAL, "rr_policy_bootstrap: params must be 16-B aligned");
+    if (obs_dim == 7 && act_dim == 4) {  // the Categorical policy's image (rr_policy_pack_discrete): its unit's kernel
+        if (precision != RR_POLICY_FP32)
+            return fail(RR_EINVAL, "rr_policy_bootstrap: (obs_dim, act_dim) = (7, 4) is RR_POLICY_FP32 only");
+        DiscreteLaunch D = {};
+        D.op = kDiscBootstrap;
+        D.params = params;
+        D.n = n;
+        D.prev_term_obs = term_obs;
+        D.prev_trunc = truncated;
+        D.prev_reward = reward;
+        D.gamma = gamma;
+        D.reward_out = reward_out;
+        D.obs = obs;
+        D.value_out = value_out;
+        const hipError_t err = (hipError_t)rrc_launch_discrete(&D, stream);
+        return err == hipSuccess ? RR_OK : hip_fail(err, "rr_policy_bootstrap: launch");
+    }
     const dim3 grid((unsigned)((n + pol::kEnvsPerBlock - 1) / pol::kEnvsPerBlock)), block(pol::kThreads);
     hipStream_t s = (hipStream_t)stream;
     const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto o, auto a, auto p) {
@@ -1975,6 +1993,184 @@ int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* g
     L.flags = flags;
     const hipError_t err = (hipError_t)rrc_launch_bc(&L, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_bc_update: launch");
+}
+
+// ---- the Categorical policy (discrete/rocket_discrete.hip): obs_dim 7, 2 .. 4 choices on <7, 4> images ----
+namespace {
+using DiscPart = ppo::Part<7, 4>;
+using DiscPack = ppo::Pack<7, 4>;
+constexpr int64_t kDiscFin = (DiscPart::SIZE + kFinElems - 1) / kFinElems;
+constexpr int64_t kDiscSink = 64 * 4 + 4 + 4;  // floats: heads >= n_choices' weight and bias sums, log_std's slot
+
+int disc_shape_ok(const char* who, int obs_dim, int n_choices)
+{
+    if (obs_dim != 7) return refuse(who, "obs_dim must be 7 (the 3DOF env)");
+    if (n_choices < 2 || n_choices > 4) return refuse(who, "n_choices must be in 2 .. 4");
+    return RR_OK;
+}
+
+// rr_ppo_update's sections at <7, 4> (ppo_carve), then the finish's sums and the sink
+int64_t disc_grad_bytes(int64_t batch)
+{
+    return (int64_t)(2 * ppo::kAdvPart * sizeof(double)) +
+           2 * (ppo_nwg(batch) * DiscPart::SIZE + DiscPack::SIZE) * (int64_t)sizeof(float);
+}
+int64_t disc_norm_bytes() { return (2 * kDiscFin + 1 + 3) / 4 * 16; }
+}  // namespace
+
+int rr_policy_layout_discrete(int obs_dim, int64_t* off)
+{
+    if (obs_dim != 7) return fail(RR_EINVAL, "rr_policy_layout_discrete: obs_dim must be 7 (the 3DOF env)");
+    using LL = pol::Layout<7, 4, 0>;
+    if (off) {
+        const int64_t v[12] = {LL::L1A, LL::B1, LL::L2A, LL::B2, LL::TOWER, LL::PI,
+                               LL::VF,  LL::HA, LL::HV,  LL::HB, LL::VB,    LL::LS};
+        for (int k = 0; k < 12; ++k) off[k] = v[k];
+    }
+    return LL::SIZE;
+}
+
+int rr_policy_pack_discrete(int obs_dim, int n_choices, const float* const* src, float* params, void* stream)
+{
+    if (const int rc = disc_shape_ok("rr_policy_pack_discrete", obs_dim, n_choices); rc != RR_OK) return rc;
+    if (!src || !params) return fail(RR_EINVAL, "rr_policy_pack_discrete: null argument");
+    DiscreteLaunch D = {};
+    D.op = kDiscPack;
+    D.n_choices = n_choices;
+    for (int k = 0; k < 12; ++k) {
+        if (!src[k]) return fail(RR_EINVAL, "rr_policy_pack_discrete: null parameter tensor");
+        D.u.ps.p[k] = src[k];
+    }
+    D.u.pack = params;
+    D.n = 1;
+    const hipError_t err = (hipError_t)rrc_launch_discrete(&D, stream);
+    return err == hipSuccess ? RR_OK : hip_fail(err, "rr_policy_pack_discrete: launch");
+}
+
+int rr_policy_act_discrete(const float* params, int obs_dim, int n_choices, const float* table, int precision,
+                           int64_t n, int64_t env_id_offset, const float* obs, uint64_t seed, const uint64_t* iter,
+                           int t, float* action_env, float* action, float* value, float* log_prob, float* obs_copy,
+                           const float* prev_term_obs, const uint8_t* prev_truncated, const float* prev_reward,
+                           float gamma, float* reward_out, const uint8_t* done, float* start_out, void* stream)
+{
+    const char* who = "rr_policy_act_discrete";
+    if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
+    if (precision != RR_POLICY_FP32) return refuse(who, "precision must be RR_POLICY_FP32");
+    if (!params || !table || !obs || !iter || !action_env || !action || !value || !log_prob || n <= 0)
+        return refuse(who, "null argument or n <= 0");
+    if (reward_out && (!prev_term_obs || !prev_truncated || !prev_reward))
+        return refuse(who, "reward_out needs prev_term_obs, prev_truncated, prev_reward");
+    if (start_out && !done) return refuse(who, "start_out needs done");
+    if (((uintptr_t)params & 15) != 0) return refuse(who, "params must be 16-B aligned");
+    DiscreteLaunch D = {};
+    D.op = kDiscAct;
+    D.n_choices = n_choices;
+    for (int k = 0; k < n_choices; ++k)
+        for (int c = 0; c < 2; ++c) {
+            if (!std::isfinite(table[2 * k + c])) return refuse(who, "table entries must be finite");
+            D.table[k][c] = table[2 * k + c];
+        }
+    const uint64_t mixed = splitmix64(seed);  // as rr_policy_act: the same noise key
+    D.seed_lo = (uint32_t)mixed;
+    D.seed_hi = (uint32_t)(mixed >> 32);
+    D.params = params;
+    D.n = n;
+    D.id_off = env_id_offset;
+    D.obs = obs;
+    D.iter = iter;
+    D.t = (uint32_t)t;
+    D.act_env = action_env;
+    D.act = action;
+    D.value = value;
+    D.logp = log_prob;
+    D.obs_copy = obs_copy;
+    D.prev_term_obs = prev_term_obs;
+    D.prev_trunc = prev_truncated;
+    D.prev_reward = prev_reward;
+    D.gamma = gamma;
+    D.reward_out = reward_out;
+    D.done = done;
+    D.start_out = start_out;
+    const hipError_t err = (hipError_t)rrc_launch_discrete(&D, stream);
+    return err == hipSuccess ? RR_OK : hip_fail(err, "rr_policy_act_discrete: launch");
+}
+
+int rr_ppo_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes)
+{
+    const char* who = "rr_ppo_update_discrete_workspace_size";
+    if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
+    if (batch < 2 || !bytes) return refuse(who, "batch >= 2 and bytes required");
+    *bytes = (disc_grad_bytes(batch) + 15) / 16 * 16 + disc_norm_bytes() + kDiscSink * (int64_t)sizeof(float);
+    return RR_OK;
+}
+
+int rr_ppo_update_discrete(int obs_dim, int n_choices, float* const* params, float* const* grads,
+                           float* const* exp_avg, float* const* exp_avg_sq, float* const* step, const float* obs,
+                           const float* actions, const float* old_log_prob, const float* advantages,
+                           const float* returns, const int64_t* idx, int64_t batch, const int64_t* next_idx,
+                           int64_t next_batch, float clip_range, float ent_coef, float vf_coef, float max_grad_norm,
+                           const float* lr, double beta1, double beta2, float eps, float* stats, uint32_t flags,
+                           void* workspace, int64_t workspace_bytes, void* stream)
+{
+    const char* who = "rr_ppo_update_discrete";
+    int64_t need = 0;
+    if (const int rc = rr_ppo_update_discrete_workspace_size(obs_dim, n_choices, batch, &need); rc != RR_OK) {
+        if (obs_dim == 7 && n_choices >= 2 && n_choices <= 4) return refuse(who, "batch >= 2 required");
+        return disc_shape_ok(who, obs_dim, n_choices);
+    }
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !obs || !actions || !old_log_prob || !advantages ||
+        !returns || !idx || !lr)
+        return refuse(who, "null argument");
+    if (const int rc = learner_ws_ok(who, workspace, workspace_bytes, need, flags, RR_PPO_CHAINED); rc != RR_OK) return rc;
+    if (!(clip_range >= 0.0f)) return refuse(who, "clip_range must be >= 0");
+    if (next_idx && !(next_batch >= 2 && next_batch <= batch)) return refuse(who, "next_batch must be in [2, batch]");
+    DiscreteLaunch D = {};
+    D.op = kDiscUpdate;
+    D.n_choices = n_choices;
+    PpoLaunch& L = D.u;
+    L.op = 1;
+    const int64_t numel[12] = {64 * 7, 64, 64 * 64, 64, 64 * 7, 64, 64 * 64, 64, 64 * n_choices, n_choices, 64, 1};
+    L.a.n = 12;
+    for (int k = 0; k < 12; ++k) {
+        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || !step[k])
+            return refuse(who, "null parameter, gradient or optimizer-state tensor");
+        L.ps.p[k] = params[k];
+        L.pg.p[k] = grads[k];
+        L.a.param[k] = params[k];
+        L.a.grad[k] = grads[k];
+        L.a.exp_avg[k] = exp_avg[k];
+        L.a.exp_avg_sq[k] = exp_avg_sq[k];
+        L.a.step[k] = step[k];
+        L.a.start[k + 1] = L.a.start[k] + numel[k];
+        L.a.wstart[k + 1] = L.a.wstart[k] + (numel[k] + kWave - 1) / kWave * kWave;
+    }
+    L.obs_dim = obs_dim;
+    L.nwg = (int)ppo_nwg(batch);
+    L.adv_part = (double*)workspace;
+    L.pack = (float*)((char*)workspace + 2 * ppo::kAdvPart * sizeof(double));
+    L.part = L.pack + 2 * DiscPack::SIZE;
+    L.normw = (float*)((char*)workspace + (disc_grad_bytes(batch) + 15) / 16 * 16);
+    D.sink = (float*)((char*)L.normw + disc_norm_bytes());
+    L.pg.p[12] = D.sink + 64 * 4 + 4;
+    L.nbp = (int)((L.a.wstart[12] + kAdamThreads - 1) / kAdamThreads);
+    L.obs = obs;
+    L.actions = actions;
+    L.old_log_prob = old_log_prob;
+    L.advantages = advantages;
+    L.returns = returns;
+    L.idx = idx;
+    L.next_idx = next_idx;
+    L.batch = batch;
+    L.next_batch = next_batch;
+    L.clip = clip_range;
+    L.ent = ent_coef;
+    L.vf = vf_coef;
+    L.max_norm = max_grad_norm;
+    set_adam(L, lr, beta1, beta2, eps);
+    L.stats = stats;
+    L.flags = flags & RR_PPO_CHAINED;
+    const hipError_t err = (hipError_t)rrc_launch_discrete(&D, stream);
+    return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_discrete: launch");
 }
 
 }  // extern "C"

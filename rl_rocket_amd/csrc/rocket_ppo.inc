@@ -44,7 +44,8 @@
 // them with the options on, in kernels of its own: ppo_prep_body and ppo_grad_tower as functions,
 // the finish and optimizer bodies as included text (rocket_ppo_finish_body.inc).
 // bc/rocket_bc.hip (rr_bc_update, behaviour cloning) instantiates the pi tower with LOSS 1 and
-// includes the same two bodies.
+// includes the same two bodies; discrete/rocket_discrete.hip (rr_ppo_update_discrete, the Categorical
+// policy) the pi tower with LOSS 2 over <7, 4> and the same two bodies.
 #pragma once
 
 #include <type_traits>
@@ -99,7 +100,7 @@ struct Part {
     static constexpr int HW = B2 + 64;          // [ACT][64 unit] (vf: row 0)
     static constexpr int HB = HW + 64 * ACT;    // [4]
     static constexpr int LS = HB + 4;           // [4] (pi)
-    static constexpr int ST = LS + 4;           // pi: pg sum, clip count, approx-kl sum; vf: squared-error sum
+    static constexpr int ST = LS + 4;           // pi: pg sum, clip count, approx-kl sum (LOSS 2: + entropy sum); vf: squared-error sum
     static constexpr int SIZE = ST + 4;
     static_assert(SIZE % 4 == 0, "16-B rows");
 };
@@ -277,13 +278,20 @@ __global__ __launch_bounds__(256) void ppo_prep_kernel(const float* __restrict__
 // LOSS 1 (behaviour cloning, bc/rocket_bc.hip; pi tower, NORM false): loss = -mean(log_prob(a)), so
 // d loss / d log_prob = -1 / B for every sample: no ratio, no clip; old_lp / adv are not read, and
 // the three sums are -log_prob, exp(log_prob) and a spare.
+// LOSS 2 (Categorical policy, discrete/rocket_discrete.hip; pi tower over <OBS, 4>): the heads are the
+// logits of the first n_choices choices, act holds one float per row (the chosen index, compared
+// against k, never used as an address), log_prob = logit_a - logsumexp. PPO's ratio lines are LOSS 0's.
+// The entropy H = -sum_k p_k log p_k depends on the state, so its gradient is part of the head
+// derivative here (ent_coef is an argument; the Gaussian kernels' finish adds theirs to log_std):
+//   dz_k = dlp ((k == a) - p_k) + ent_coef / B p_k (log p_k + H),   0 for k >= n_choices;
+// nothing goes to the log_std sums, and a fourth per-sample sum carries H.
 template <int OBS, int ACT, int TW, bool VCLIP = false, bool NORM = true, int LOSS = 0>
 __device__ __forceinline__ void ppo_grad_tower(
     float* __restrict__ lds, const float* __restrict__ obs, const float* __restrict__ act,
     const float* __restrict__ old_lp, const float* __restrict__ adv, const float* __restrict__ ret,
     const int64_t* __restrict__ idx, int64_t bs, float clip, float vf_coef, const double* __restrict__ adv_part,
     const float* __restrict__ pack, float* __restrict__ part, const float* __restrict__ old_val = nullptr,
-    float clip_vf = 0.0f)
+    float clip_vf = 0.0f, int n_choices = 0, float ent_coef = 0.0f)
 {
     using L = pol::Layout<OBS, ACT, 0>;
     using K = ppo::Pack<OBS, ACT>;
@@ -321,9 +329,13 @@ __device__ __forceinline__ void ppo_grad_tower(
             in.x[k] = col < OBS ? obs[r * OBS + col] : 0.0f;
         }
         if (tw == 0) {
+            if constexpr (LOSS == 2) {
+                in.a[0] = act[r];  // the chosen index
+            } else {
 #pragma unroll
-            for (int a = 0; a < ACT; ++a) in.a[a] = act[r * ACT + a];
-            if constexpr (LOSS == 0) {
+                for (int a = 0; a < ACT; ++a) in.a[a] = act[r * ACT + a];
+            }
+            if constexpr (LOSS != 1) {
                 in.olp = old_lp[r];
                 in.av = adv[r];
             }
@@ -391,6 +403,7 @@ __device__ __forceinline__ void ppo_grad_tower(
         for (int r = 0; r < 16; ++r) accW1[b][r] = 0.0f;
     float hw_acc[ACT], hb_acc[ACT], ls_acc[ACT], b2_acc = 0.0f;
     float st0 = 0.0f, st1 = 0.0f, st2 = 0.0f;
+    [[maybe_unused]] float st3 = 0.0f;  // LOSS 2: the entropy sum
 #pragma unroll
     for (int a = 0; a < ACT; ++a) hw_acc[a] = hb_acc[a] = ls_acc[a] = 0.0f;
     float ls[ACT], var[ACT];
@@ -430,11 +443,39 @@ __device__ __forceinline__ void ppo_grad_tower(
             else if constexpr (NORM) A = valid ? ((in.av - a_mean) - a_mean_lo) / a_den : 0.0f;
             else A = valid ? in.av : 0.0f;
             float lp = 0.0f, d[ACT];
+            [[maybe_unused]] float pr[ACT], lpk[ACT], H = 0.0f;
+            if constexpr (LOSS == 2) {
+                // softmax over the first n_choices logits: log p_k from the log of the sum, so that a
+                // p_k that underflows to 0 leaves log p_k finite
+                float z[ACT];
 #pragma unroll
-            for (int a = 0; a < ACT; ++a) {
-                const float mean = pol::head_dot<1>(sp + K::HW + a * 64, h2, 0, half) + sp[K::HB + a];
-                d[a] = in.a[a] - mean;
-                lp += -(d[a] * d[a]) / var[a] - ls[a] - 0.918938533204672742f;
+                for (int a = 0; a < ACT; ++a) z[a] = pol::head_dot<1>(sp + K::HW + a * 64, h2, 0, half) + sp[K::HB + a];
+                float zm = z[0];
+#pragma unroll
+                for (int a = 1; a < ACT; ++a) zm = a < n_choices ? fmaxf(zm, z[a]) : zm;
+                float sum = 0.0f;
+#pragma unroll
+                for (int a = 0; a < ACT; ++a) {
+                    pr[a] = a < n_choices ? expf(z[a] - zm) : 0.0f;
+                    sum += pr[a];
+                }
+                const float lse = logf(sum);
+#pragma unroll
+                for (int a = 0; a < ACT; ++a) {
+                    lpk[a] = (z[a] - zm) - lse;
+                    pr[a] = pr[a] / sum;
+                    if (a < n_choices) {
+                        if (in.a[0] == (float)a) lp = lpk[a];
+                        if (pr[a] > 0.0f) H -= pr[a] * lpk[a];
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int a = 0; a < ACT; ++a) {
+                    const float mean = pol::head_dot<1>(sp + K::HW + a * 64, h2, 0, half) + sp[K::HB + a];
+                    d[a] = in.a[a] - mean;
+                    lp += -(d[a] * d[a]) / var[a] - ls[a] - 0.918938533204672742f;
+                }
             }
             // d loss / d lp; PPO's ratio terms are read again by its sums below
             float dlp, lr, r, u, c;
@@ -450,13 +491,24 @@ __device__ __forceinline__ void ppo_grad_tower(
                 const float mask = (r >= lo && r <= hi) ? 1.0f : 0.0f;
                 dlp = valid ? -inv_b * (A * gu + A * gc * mask) * r : 0.0f;
             }
+            if constexpr (LOSS == 2) {
+                // d lp / d z_k = (k == a) - p_k; d(-H) / d z_k = p_k (log p_k + H)
+                const float ec = valid ? ent_coef * inv_b : 0.0f;
 #pragma unroll
-            for (int a = 0; a < ACT; ++a) {
-                // d lp / d mean = 2 d / (2 std^2); d lp / d log_std = d^2 / std^2 - 1
-                dh[a] = dlp * (2.0f * d[a] / var[a]);
-                if (half == 0) {
-                    hb_acc[a] += dh[a];
-                    ls_acc[a] += dlp * (2.0f * d[a] * d[a] / var[a] - 1.0f);
+                for (int a = 0; a < ACT; ++a) {
+                    const float hit = in.a[0] == (float)a ? 1.0f : 0.0f;
+                    dh[a] = a < n_choices ? dlp * (hit - pr[a]) + ec * (pr[a] * (lpk[a] + H)) : 0.0f;
+                    if (half == 0) hb_acc[a] += dh[a];
+                }
+            } else {
+#pragma unroll
+                for (int a = 0; a < ACT; ++a) {
+                    // d lp / d mean = 2 d / (2 std^2); d lp / d log_std = d^2 / std^2 - 1
+                    dh[a] = dlp * (2.0f * d[a] / var[a]);
+                    if (half == 0) {
+                        hb_acc[a] += dh[a];
+                        ls_acc[a] += dlp * (2.0f * d[a] * d[a] / var[a] - 1.0f);
+                    }
                 }
             }
             if (half == 0 && valid) {
@@ -467,6 +519,7 @@ __device__ __forceinline__ void ppo_grad_tower(
                     st0 -= fminf(u, c);
                     st1 += fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
                     st2 += (r - 1.0f) - lr;
+                    if constexpr (LOSS == 2) st3 += H;
                 }
             }
         } else {
@@ -641,6 +694,7 @@ __device__ __forceinline__ void ppo_grad_tower(
     st0 = ppo::wave_sum(st0);
     st1 = ppo::wave_sum(st1);
     st2 = ppo::wave_sum(st2);
+    if constexpr (LOSS == 2) st3 = ppo::wave_sum(st3);
     __syncthreads();  // every wave is done with its tiles: LDS becomes the reduction buffer
     float* red = lds + wv * PT::SIZE;
 #pragma unroll
@@ -664,7 +718,7 @@ __device__ __forceinline__ void ppo_grad_tower(
             }
         red[PT::HB + lane] = hb;
         red[PT::LS + lane] = l;
-        red[PT::ST + lane] = lane == 0 ? st0 : lane == 1 ? st1 : lane == 2 ? st2 : 0.0f;
+        red[PT::ST + lane] = lane == 0 ? st0 : lane == 1 ? st1 : lane == 2 ? st2 : (LOSS == 2 ? st3 : 0.0f);
     }
     __syncthreads();
     // the four waves' vectors summed as 16-B rows (PT::SIZE % 4 == 0: every row 16-B aligned)
@@ -821,6 +875,30 @@ struct BcLaunch {
     uint32_t flags;
 };
 static_assert(std::is_trivially_copyable_v<BcLaunch>, "BcLaunch crosses TUs by memcpy");
+
+// What the main TU hands to discrete/rocket_discrete.hip (rrc_launch_discrete), by `op`:
+//   kDiscAct        rr_policy_act_discrete: one discrete_act_kernel launch
+//   kDiscUpdate     rr_ppo_update_discrete: `u`, an rr_ppo_update record (op 1) over 12 tensors whose
+//                   pg.p[12] is four spare floats of the workspace, and `sink`, 260 more (where the
+//                   finish puts the zero sums of heads >= n_choices)
+//   kDiscPack       rr_policy_pack_discrete: the rollout image of pol::Layout<7, 4, 0>
+//   kDiscBootstrap  rr_policy_bootstrap at (7, 4): policy_bootstrap_kernel<7, 4, 0>
+enum { kDiscAct = 0, kDiscUpdate, kDiscPack, kDiscBootstrap };
+struct DiscreteLaunch {
+    int op, n_choices;
+    float table[4][2];  // act: the choices' [gimbal, thrust] rows
+    PpoLaunch u;        // update; pack: u.ps, u.pack
+    float* sink;        // update
+    // act / bootstrap
+    const float *params, *obs, *prev_term_obs, *prev_reward;
+    const uint8_t *prev_trunc, *done;
+    const uint64_t* iter;
+    float *act_env, *act, *value, *logp, *obs_copy, *reward_out, *start_out, *value_out;
+    int64_t n, id_off;
+    uint32_t seed_lo, seed_hi, t;
+    float gamma;
+};
+static_assert(std::is_trivially_copyable_v<DiscreteLaunch>, "DiscreteLaunch crosses TUs by memcpy");
 
 // Element k of policy tensor t (rr_ppo_grad order) into the packed images (two towers of Pack::SIZE).
 template <int OBS, int ACT>

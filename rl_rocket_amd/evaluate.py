@@ -4,7 +4,8 @@ import torch
 from ._lib import (RR_EVAL_BOUNDS as EVAL_BOUNDS, RR_EVAL_EVENT as EVAL_EVENT, RR_EVAL_LANDED as EVAL_LANDED,
                    RR_EVAL_NONFINITE as EVAL_NONFINITE, RR_EVAL_TRUNCATED as EVAL_TRUNCATED)
 from .eval_trace import EpisodeRecord, EvalTrace  # noqa: F401
-from .policy import POLICY_PRECISIONS, MlpActorCritic, PolicyPack, fused_grad_supported
+from .policy import (POLICY_PRECISIONS, MlpActorCritic, MlpCategoricalActorCritic, PolicyPack,
+                     fused_grad_supported)
 
 
 class EvalResult:
@@ -87,7 +88,12 @@ class PolicyEvaluator:
     (default ``max_episode_steps``; required without a TimeLimit): longer episodes are clipped, their
     ``length`` still counts every step. An episode's step count starts at the call, and the v_targ
     history takes v_0 from the first recorded state: reset first, as for whole episodes.
-    ``record=None`` is the plain evaluation (``rr_policy_evaluate``)."""
+    ``record=None`` is the plain evaluation (``rr_policy_evaluate``).
+
+    A ``MlpCategoricalActorCritic`` (discrete 3DOF actions) runs through the step-by-step path
+    (``fused=False``, chosen automatically) with the action ``policy.continuous(policy.mode(logits))``,
+    SB3's deterministic prediction behind ``DiscreteActions3DOF``; ``fused=True`` and ``record=``
+    raise for it (there is no fused evaluation kernel with a Categorical head)."""
 
     def __init__(self, batch, policy, n_episodes=5, max_steps=None, policy_dtype="fp32", fused=None, record=None,
                  record_steps=None):
@@ -96,6 +102,14 @@ class PolicyEvaluator:
 
         self.env, self.policy = batch, policy
         n, ns, na = batch.num_envs, batch.state_dim, batch.action_dim
+        self._discrete = isinstance(policy, MlpCategoricalActorCritic)
+        if self._discrete:
+            if ns != 7 or na != 2:
+                raise ValueError("a Categorical policy drives the 3DOF env (its table rows are [gimbal, thrust])")
+            if fused or record is not None:
+                raise ValueError("%s is not available for a Categorical policy: it is evaluated step by step "
+                                 "(fused=False), without recording" % ("fused=True" if fused else "record="))
+            fused = False
         dev = batch.device
         p = batch.params
         if not p.flags & _lib.RR_FLAG_AUTO_RESET:
@@ -238,7 +252,7 @@ class PolicyEvaluator:
 
     def _mean(self, obs):
         pol = self.policy
-        if isinstance(pol, MlpActorCritic):
+        if isinstance(pol, (MlpActorCritic, MlpCategoricalActorCritic)):
             return pol.action_net(pol.pi_net(obs))  # the pi tower only
         return pol(obs)[0]
 
@@ -264,7 +278,10 @@ class PolicyEvaluator:
         m0 = pre[0][-1].float()
         for _ in range(self.max_steps):
             active = ep < ne
-            act = torch.clamp(self._mean(obs), -1.0, 1.0)
+            if self._discrete:  # the table row of the most probable choice
+                act = self.policy.continuous(self.policy.mode(self._mean(obs)))
+            else:
+                act = torch.clamp(self._mean(obs), -1.0, 1.0)
             (sh.set_state64 if self._dopri else sh.set_state)(pre[0], v0=pre[1], elapsed=pre[2] & el_mask)
             sh.step(act)
             y1 = (sh.get_state64() if self._dopri else sh.get_state())[0].float()

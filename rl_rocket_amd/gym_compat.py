@@ -118,6 +118,50 @@ class Box:
         return _gym.spaces.Box(low=self.low, high=self.high, dtype=self.dtype)
 
 
+class Discrete:
+    """gym 0.21 ``spaces.Discrete``: the integers 0 .. n - 1 (``sample`` is ``RandomState.randint(n)``)."""
+
+    def __init__(self, n, seed=None):
+        if not int(n) > 0:
+            raise ValueError("n must be positive")
+        self.n = int(n)
+        self.shape, self.dtype = (), np.dtype(np.int64)
+        self._np_random = None
+        if seed is not None:
+            self.seed(seed)
+
+    @property
+    def np_random(self):
+        if self._np_random is None:
+            self.seed()
+        return self._np_random
+
+    def seed(self, seed=None):
+        self._np_random, seed = np_random(seed)
+        return [seed]
+
+    def sample(self):
+        return int(self.np_random.randint(self.n))
+
+    def contains(self, x):
+        if isinstance(x, (int, np.integer)):
+            return 0 <= int(x) < self.n
+        x = np.asarray(x)
+        return bool(x.shape == () and x.dtype.kind in "iu" and 0 <= int(x) < self.n)
+
+    def __eq__(self, other):
+        return isinstance(other, Discrete) and other.n == self.n
+
+    def __repr__(self):
+        return "Discrete(%d)" % self.n
+
+    def to_gym(self):
+        """The equivalent real gym Discrete, when gym is importable."""
+        if not HAVE_GYM:
+            return self
+        return _gym.spaces.Discrete(self.n)
+
+
 def register_ids():
     """Register the reference env ids (my_environment/__init__.py:4-12) with gym, if present."""
     if not HAVE_GYM:

@@ -3,13 +3,14 @@
 ``ClipAdam``), the whole minibatch step as one library call (``PPOUpdate``) and an epoch of steps
 captured into a hipGraph (``GraphedPPOUpdate``). ``_AdamState`` is the binding of the 13 policy
 tensors and a capturable Adam's state that the fused calls share with ``bc.BCUpdate``.
+``PPOUpdateDiscrete`` is ``PPOUpdate`` for a ``MlpCategoricalActorCritic`` (``rr_ppo_update_discrete``).
 """
 import ctypes
 
 import torch
 
 from . import _lib
-from .policy import _policy_tensors, fused_grad_supported
+from .policy import MlpCategoricalActorCritic, _policy_tensors, fused_discrete_supported, fused_grad_supported
 
 
 def _check_params(who, params, dev, whose):
@@ -316,6 +317,76 @@ class PPOUpdate(PPOGrad, _AdamState):
         return self.stats
 
 
+_DISCRETE_FUSED = ("the fused Categorical learner (rr_ppo_update_discrete) is the one-replica call with a capturable "
+                   "torch.optim.Adam and SB3's defaults: %s needs fused=False (the autograd path takes it)")
+
+
+def _discrete_fused_ok(optimizer, policy, group, cvf, norm, tkl, train_stats=False):
+    """Refuses what ``fused=True`` does not take for a Categorical policy, before any device work."""
+    what = ("group=" if group is not None else "clip_range_vf" if cvf else "normalize_advantage=False" if not norm
+            else "target_kl" if tkl else "train_stats" if train_stats else None)
+    if what:
+        raise ValueError(_DISCRETE_FUSED % what)
+    if not clip_adam_supported(optimizer, list(policy.parameters())):
+        raise ValueError(_DISCRETE_FUSED % "another optimizer")
+
+
+class PPOUpdateDiscrete(_AdamState):
+    """``PPOUpdate`` for a ``MlpCategoricalActorCritic`` on a 3DOF rollout: one PPO minibatch step with a
+    Categorical distribution as ONE library call (``rr_ppo_update_discrete``: the learner's towers
+    with a softmax head, the entropy's gradient per sample, clip + Adam over the policy's 12
+    tensors). ``__call__(idx, next_idx=None, chained=False)`` and ``stats`` are ``PPOUpdate``'s;
+    ``stats[2]`` is the minibatch's mean entropy. SB3's defaults only: no ``clip_range_vf``,
+    ``target_kl``, raw advantages or control block (``opts`` is None)."""
+
+    opts = None
+
+    def __init__(self, policy, optimizer, ro, batch_size, clip_range=0.2, ent_coef=0.01, vf_coef=0.5,
+                 max_grad_norm=0.5):
+        n = ro.n_steps * ro.env.num_envs
+        ns = ro.env.state_dim
+        if not fused_discrete_supported(policy, ns):
+            raise ValueError("PPOUpdateDiscrete needs an MlpCategoricalActorCritic with 64x64 towers and 2 .. 4 "
+                             "choices on a 3DOF rollout")
+        if not 2 <= batch_size <= n:
+            raise ValueError("batch_size must be in [2, n_steps * num_envs]")
+        if not clip_adam_supported(optimizer, list(policy.parameters())):
+            raise ValueError("PPOUpdateDiscrete needs a capturable torch.optim.Adam over the policy's parameters "
+                             "(one group, no weight decay / amsgrad / maximize)")
+        self._lib = _lib.load()
+        self.ns, self.na, self.bs = ns, policy.n_choices, int(batch_size)
+        self.coef = (float(clip_range), float(ent_coef), float(vf_coef))
+        self.max_norm = float(max_grad_norm) if max_grad_norm is not None else 0.0
+        dev = ro.obs.device
+        self.data = [ro.obs.reshape(n, ns), ro.actions.reshape(n), ro.log_probs.reshape(n),
+                     ro.advantages.reshape(n), ro.returns.reshape(n)]
+        for t in self.data:
+            if not t.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError("rollout tensors must be contiguous fp32")
+        self.params = _policy_tensors(policy)
+        _check_params("rr_ppo_update_discrete", self.params, dev, "rollout")
+        self._bind_adam(optimizer, self.params)
+        self.ws, self._nbytes = _workspace(self._lib, "rr_ppo_update_discrete_workspace_size", dev, ns, self.na, self.bs)
+        self.stats = torch.zeros(5, dtype=torch.float32, device=dev)
+        self._next = None
+
+    def __call__(self, idx, next_idx=None, chained=False):
+        for t in (idx,) if next_idx is None else (idx, next_idx):
+            _check_idx(t, self.bs, self.ws.device, False, "idx / next_idx must be contiguous int64 device tensors")
+        if next_idx is not None and next_idx.numel() > idx.numel():
+            raise ValueError("next_idx may not be longer than idx")
+        if chained and self._next != (idx.data_ptr(), idx.numel()):
+            raise ValueError("chained=True needs the previous call on this PPOUpdateDiscrete to have had next_idx=idx")
+        nxt = None if next_idx is None else (next_idx.data_ptr(), next_idx.numel())
+        _lib.check(self._lib.rr_ppo_update_discrete(
+            self.ns, self.na, *self._ptrs, *[t.data_ptr() for t in self.data], idx.data_ptr(), idx.numel(),
+            *(nxt or (None, 0)), *self.coef, self.max_norm, *self._adam_args(), self.stats.data_ptr(),
+            _lib.RR_PPO_CHAINED if chained else 0, self.ws.data_ptr(), self._nbytes, _stream(self.ws.device)),
+            "rr_ppo_update_discrete")
+        self._next = nxt
+        return self.stats
+
+
 def _epoch_perms(n, n_epochs, dev, generator=None):
     """The epochs' permutations for the fused updates, each later one drawn on a side stream
     while the caller runs the previous epoch on the current stream (torch's randperm at 1 M rows
@@ -352,7 +423,10 @@ def _ppo_loss(policy, obs, act, old_lp, adv, ret, old_v, n_rows, clip_range, ent
     if cvf:
         value = old_v + torch.clamp(value - old_v, -cvf, cvf)
     vf = torch.nn.functional.mse_loss(ret, value)
-    ent = -policy.entropy(n_rows).mean()
+    if isinstance(policy, MlpCategoricalActorCritic):  # state dependent: from the logits (`mean` holds them)
+        ent = -policy.entropy(mean).mean()
+    else:
+        ent = -policy.entropy(n_rows).mean()
     loss = pg + ent_coef * ent + vf_coef * vf
     return loss, {"policy_loss": pg.detach(), "value_loss": vf.detach(), "entropy": -ent.detach()}, lp, ratio
 
@@ -380,9 +454,17 @@ def ppo_update(policy, optimizer, ro, n_epochs=10, batch_size=65536, clip_range=
     ``target_kl`` with SB3's ``break``. ``fused=True`` takes them on the one-replica path with a
     capturable Adam (``PPOUpdate``: ``rr_ppo_update_opts``, the stop carried on the device) and
     refuses them elsewhere. ``target_kl`` with a ``group`` is refused everywhere: every rank would
-    decide on its own minibatch's KL."""
+    decide on its own minibatch's KL.
+
+    A ``MlpCategoricalActorCritic`` (discrete 3DOF actions): the autograd path takes everything above,
+    with the entropy from the logits. ``fused=True`` is ``PPOUpdateDiscrete``
+    (``rr_ppo_update_discrete``, chained) and needs a capturable Adam and no ``group``;
+    ``clip_range_vf``, ``normalize_advantage=False`` and ``target_kl`` raise there."""
     n = ro.n_steps * ro.env.num_envs
     cvf, norm, tkl = _ppo_options(clip_range_vf, normalize_advantage, target_kl)
+    disc = isinstance(policy, MlpCategoricalActorCritic)
+    if fused and disc:
+        _discrete_fused_ok(optimizer, policy, group, cvf, norm, tkl)
     if tkl and group is not None:
         raise ValueError("target_kl with a group is not supported: the ranks would stop at different minibatches")
     if fused and (cvf or tkl or not norm) and (group is not None
@@ -401,8 +483,10 @@ def ppo_update(policy, optimizer, ro, n_epochs=10, batch_size=65536, clip_range=
         stats = None
         if group is None and clip_adam_supported(optimizer, params):
             # the whole minibatch step in one call, chained: each call sums the next one's statistics
-            step = PPOUpdate(policy, optimizer, ro, min(batch_size, n), clip_range, ent_coef, vf_coef, max_grad_norm,
-                             clip_range_vf, normalize_advantage, target_kl)
+            step = (PPOUpdateDiscrete(policy, optimizer, ro, min(batch_size, n), clip_range, ent_coef, vf_coef,
+                                      max_grad_norm) if disc else
+                    PPOUpdate(policy, optimizer, ro, min(batch_size, n), clip_range, ent_coef, vf_coef, max_grad_norm,
+                              clip_range_vf, normalize_advantage, target_kl))
             kw = {}
             for perm in perms:
                 for s in range(0, n, step.bs):
@@ -486,7 +570,11 @@ class GraphedPPOUpdate:
     epochs after it replay as no-ops, and ``update`` still never waits for the device on their
     account. ``train_stats()`` returns SB3's ``train/*`` means over the last ``update`` with one
     copy. ``fused=False`` captures ``clip_range_vf`` and ``normalize_advantage`` as PyTorch ops and
-    refuses ``target_kl`` (a ``break`` cannot be captured); the split multi-GPU path refuses all."""
+    refuses ``target_kl`` (a ``break`` cannot be captured); the split multi-GPU path refuses all.
+
+    A ``MlpCategoricalActorCritic``: ``fused`` defaults to True where ``PPOUpdateDiscrete`` applies
+    (one replica, capturable Adam, SB3's defaults) and captures its chained calls; the options and
+    ``group`` raise with ``fused=True`` and are captured as PyTorch ops with ``fused=False``."""
 
     def __init__(self, policy, optimizer, ro, batch_size=65536, clip_range=0.2, ent_coef=0.01, vf_coef=0.5,
                  max_grad_norm=0.5, group=None, fused=None, clip_range_vf=None, normalize_advantage=True,
@@ -495,6 +583,13 @@ class GraphedPPOUpdate:
             raise ValueError("GraphedPPOUpdate needs an optimizer with capturable=True")
         cvf, norm, tkl = _ppo_options(clip_range_vf, normalize_advantage, target_kl)
         self._opt = (cvf, norm, tkl)
+        disc = isinstance(policy, MlpCategoricalActorCritic)
+        if fused is None and disc:
+            fused = (fused_discrete_supported(policy, ro.env.state_dim) and group is None
+                     and not (cvf or tkl or not norm or train_stats)
+                     and clip_adam_supported(optimizer, list(policy.parameters())))
+        if fused and disc:
+            _discrete_fused_ok(optimizer, policy, group, cvf, norm, tkl, train_stats)
         if tkl and group is not None:
             raise ValueError("target_kl with a group is not supported: the ranks would stop at different minibatches")
         n = ro.n_steps * ro.env.num_envs
@@ -540,7 +635,9 @@ class GraphedPPOUpdate:
         self.old_v = _old_values(ro, n) if cvf and not self.fused else None
         # fused, one replica, capturable Adam: the chained whole-minibatch call (rr_ppo_update, or
         # rr_ppo_update_opts with an option or train_stats)
-        self._update = (PPOUpdate(policy, optimizer, ro, batch_size, clip_range, ent_coef, vf_coef, max_grad_norm,
+        self._update = (PPOUpdateDiscrete(policy, optimizer, ro, batch_size, clip_range, ent_coef, vf_coef, max_grad_norm)
+                        if one_call and disc else
+                        PPOUpdate(policy, optimizer, ro, batch_size, clip_range, ent_coef, vf_coef, max_grad_norm,
                                   clip_range_vf, normalize_advantage, target_kl, train_stats)
                         if one_call else None)
         self._grad = (PPOGrad(policy, ro, batch_size, clip_range, ent_coef, vf_coef)

@@ -244,3 +244,8 @@ def lower(cfg, max_episode_steps=0, auto_reset=True, episode_stats=True, reward_
             p.att_limit[j] = 2 * math.pi
             p.land_att_limit[j] = 0.2
     return p
+
+
+# DiscreteActions3DOF's default table (reference wrappers.py:25), rows of [gimbal, thrust]: engine off,
+# full thrust gimballed to one side, straight, to the other side
+DISCRETE_TABLE_3DOF = ((0.0, -1.0), (-1.0, 1.0), (0.0, 1.0), (1.0, 1.0))

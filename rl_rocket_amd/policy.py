@@ -4,11 +4,16 @@
 ``"MlpPolicy"`` (the reference's ``sb3_config["policy_type"]``, configuration_file.py:41):
 separate pi / vf MLPs [64, 64] with tanh, diagonal Gaussian with state-independent
 log_std (init 0), orthogonal init (gain sqrt(2) hidden, 0.01 policy head, 1 value head).
+``MlpCategoricalActorCritic`` is the policy SB3 builds behind the reference's ``DiscreteActions3DOF``
+(wrappers.py:24-35, a ``Discrete(K)`` action space): the same towers and initialisation, an action
+head of K logits, no log_std (SB3 ``CategoricalDistribution``).
 """
 import math
 
 import torch
 from torch import nn
+
+from .params import DISCRETE_TABLE_3DOF
 
 
 class _LinearFn(torch.autograd.Function):
@@ -87,6 +92,72 @@ class MlpActorCritic(nn.Module):
         return (0.5 + 0.5 * math.log(2 * math.pi) + self.log_std).sum().expand(n)
 
 
+
+
+class MlpCategoricalActorCritic(nn.Module):
+    """SB3 1.6 ``MlpPolicy`` over ``Discrete(n_choices)``: ``MlpActorCritic``'s towers and
+    initialisation (``action_net`` gain 0.01), ``action_net`` giving ``n_choices`` logits, no
+    ``log_std``. ``table`` ([n_choices][2], rows of [gimbal, thrust]) turns an index into the 3DOF
+    env's action, as ``DiscreteActions3DOF.action`` does; it is a buffer, not a parameter.
+    ``forward`` returns ``(logits, value)``; ``log_prob`` / ``entropy`` / ``mode`` are
+    ``CategoricalDistribution``'s, from a log-softmax (a probability that underflows to 0 leaves its
+    log finite and its entropy term 0)."""
+
+    def __init__(self, obs_dim, n_choices, table=DISCRETE_TABLE_3DOF, hidden=(64, 64)):
+        super().__init__()
+        self.hidden = tuple(hidden)
+        table = torch.as_tensor(table, dtype=torch.float32)
+        if table.dim() != 2 or table.shape != (n_choices, 2) or not bool(torch.isfinite(table).all()):
+            raise ValueError("table must be [n_choices][2] finite numbers (rows of [gimbal, thrust])")
+        if n_choices < 2:
+            raise ValueError("n_choices must be at least 2")
+        self.n_choices = int(n_choices)
+        self.register_buffer("table", table.clone())
+
+        def mlp():
+            layers, d = [], obs_dim
+            for h in hidden:
+                layers += [_Linear(d, h), nn.Tanh()]
+                d = h
+            return nn.Sequential(*layers)
+
+        self.pi_net, self.vf_net = mlp(), mlp()
+        self.action_net = _Linear(hidden[-1], self.n_choices)
+        self.value_net = _Linear(hidden[-1], 1)
+        for net in (self.pi_net, self.vf_net):
+            for m in net:
+                if isinstance(m, nn.Linear):
+                    nn.init.orthogonal_(m.weight, gain=math.sqrt(2))
+                    nn.init.zeros_(m.bias)
+        nn.init.orthogonal_(self.action_net.weight, gain=0.01)
+        nn.init.zeros_(self.action_net.bias)
+        nn.init.orthogonal_(self.value_net.weight, gain=1.0)
+        nn.init.zeros_(self.value_net.bias)
+
+    def forward(self, obs):
+        return self.action_net(self.pi_net(obs)), self.value_net(self.vf_net(obs)).squeeze(-1)
+
+    def value(self, obs):
+        return self.value_net(self.vf_net(obs)).squeeze(-1)
+
+    def log_prob(self, logits, actions):
+        """log p of ``actions`` (indices as floats or integers, [...] or [..., 1]) under ``logits`` [..., K]."""
+        a = actions.reshape(logits.shape[:-1]).long()
+        return torch.log_softmax(logits, dim=-1).gather(-1, a.unsqueeze(-1)).squeeze(-1)
+
+    def entropy(self, logits):
+        lp = torch.log_softmax(logits, dim=-1)
+        p = lp.exp()
+        return -torch.where(p > 0, p * lp, torch.zeros_like(p)).sum(-1)
+
+    def mode(self, logits):
+        return logits.argmax(dim=-1)
+
+    def continuous(self, index):
+        """The table rows of ``index`` ([...] integers or floats holding them): [..., 2]."""
+        return self.table[index.long()]
+
+
 POLICY_PRECISIONS = {"fp32": 0, "bf16": 1, "fp16x3": 2}  # RR_POLICY_FP32 / RR_POLICY_BF16 / RR_POLICY_FP16X3
 
 
@@ -122,7 +193,16 @@ class PolicyPack:
         self.precision, self.prec = precision, POLICY_PRECISIONS[precision]
         lib = _lib.load()
         off = (ctypes.c_int64 * 12)()
-        size = _lib.check(lib.rr_policy_layout(obs_dim, act_dim, self.prec, off), "rr_policy_layout")
+        # a Categorical policy: the 4-head image of rr_policy_layout_discrete, heads >= n_choices zero
+        self.discrete = isinstance(policy, MlpCategoricalActorCritic)
+        if self.discrete:
+            if self.prec:
+                raise ValueError("a Categorical policy packs in fp32 only, not %r" % precision)
+            if act_dim != policy.n_choices:
+                raise ValueError("act_dim is the policy's n_choices for a Categorical policy")
+            size = _lib.check(lib.rr_policy_layout_discrete(obs_dim, off), "rr_policy_layout_discrete")
+        else:
+            size = _lib.check(lib.rr_policy_layout(obs_dim, act_dim, self.prec, off), "rr_policy_layout")
         self.off = dict(zip(("L1A", "B1", "L2A", "B2", "TOWER", "PI", "VF", "HA", "HV", "HB", "VB", "LS"), list(off)))
         self.size, self.obs_dim, self.act_dim, self.policy = size, obs_dim, act_dim, policy
         self.buf = torch.zeros(size + 4, dtype=torch.float32, device=device)  # +4: 16-B alignment slack
@@ -219,8 +299,13 @@ class PolicyPack:
         from . import _lib
 
         ts = self._sources()
-        src = (ctypes.c_void_p * 13)(*[t.data_ptr() for t in ts])
+        src = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.buf.device).cuda_stream)
+        if self.discrete:
+            _lib.check(_lib.load().rr_policy_pack_discrete(self.obs_dim, self.act_dim, src,
+                                                           ctypes.c_void_p(self.buf.data_ptr()), stream),
+                       "rr_policy_pack_discrete")
+            return self.buf
         _lib.check(_lib.load().rr_policy_pack(self.obs_dim, self.act_dim, self.prec, src,
                                               ctypes.c_void_p(self.buf.data_ptr()), stream), "rr_policy_pack")
         return self.buf
@@ -242,13 +327,19 @@ class PolicyPack:
             self.buf[o["HV"]: o["HV"] + 64] = wv[0, self.b_i]
             self.buf[o["HB"]: o["HB"] + na] = p.action_net.bias
             self.buf[o["VB"]: o["VB"] + 1] = p.value_net.bias
-        self.buf[o["LS"]: o["LS"] + na] = p.log_std
+        if not self.discrete:  # (a Categorical policy's heads past n_choices and its LS slots stay zero)
+            self.buf[o["LS"]: o["LS"] + na] = p.log_std
         return self.buf
 
 
 def _policy_tensors(policy):
-    """The 13 parameter tensors in rr_policy_pack / rr_ppo_grad order."""
+    """The 13 parameter tensors in rr_policy_pack / rr_ppo_grad order (12 for a Categorical policy:
+    there is no log_std)."""
     p = policy
+    if isinstance(p, MlpCategoricalActorCritic):
+        return [p.pi_net[0].weight, p.pi_net[0].bias, p.pi_net[2].weight, p.pi_net[2].bias,
+                p.vf_net[0].weight, p.vf_net[0].bias, p.vf_net[2].weight, p.vf_net[2].bias,
+                p.action_net.weight, p.action_net.bias, p.value_net.weight, p.value_net.bias]
     return [p.pi_net[0].weight, p.pi_net[0].bias, p.pi_net[2].weight, p.pi_net[2].bias,
             p.vf_net[0].weight, p.vf_net[0].bias, p.vf_net[2].weight, p.vf_net[2].bias,
             p.action_net.weight, p.action_net.bias, p.value_net.weight, p.value_net.bias, p.log_std]
@@ -257,3 +348,9 @@ def _policy_tensors(policy):
 def fused_grad_supported(policy, obs_dim, act_dim):
     return (isinstance(policy, MlpActorCritic) and policy.hidden == (64, 64)
             and (obs_dim, act_dim) in ((14, 3), (7, 2)))
+
+
+def fused_discrete_supported(policy, obs_dim):
+    """The Categorical policy the discrete HIP calls take: 64x64 towers on the 3DOF env, 2 .. 4 choices."""
+    return (isinstance(policy, MlpCategoricalActorCritic) and policy.hidden == (64, 64) and obs_dim == 7
+            and 2 <= policy.n_choices <= 4)

@@ -19,10 +19,12 @@ import torch
 from .bc import BCUpdate, Demonstrations, bc_train  # noqa: F401
 from .evaluate import (EVAL_BOUNDS, EVAL_EVENT, EVAL_LANDED, EVAL_NONFINITE, EVAL_TRUNCATED,  # noqa: F401
                        EpisodeRecord, EvalResult, EvalTrace, PolicyEvaluator, evaluate_policy)
-from .learner import (ClipAdam, GraphedPPOUpdate, PPOGrad, PPOUpdate, _allreduce_grads, _epoch_perms,  # noqa: F401
-                      _old_values, _ppo_options, _train_stats, clip_adam_supported, ppo_update)
-from .policy import (FOLD_C, POLICY_PRECISIONS, MlpActorCritic, PolicyPack, _Linear, _LinearFn,  # noqa: F401
-                     _policy_tensors, _rowsum, fused_grad_supported)
+from .learner import (ClipAdam, GraphedPPOUpdate, PPOGrad, PPOUpdate, PPOUpdateDiscrete,  # noqa: F401
+                      _allreduce_grads, _epoch_perms, _old_values, _ppo_options, _train_stats, clip_adam_supported,
+                      ppo_update)
+from .policy import (DISCRETE_TABLE_3DOF, FOLD_C, POLICY_PRECISIONS, MlpActorCritic,  # noqa: F401
+                     MlpCategoricalActorCritic, PolicyPack, _Linear, _LinearFn, _policy_tensors, _rowsum,
+                     fused_discrete_supported, fused_grad_supported)
 
 
 class DeviceRollout:
@@ -51,17 +53,41 @@ class DeviceRollout:
     ``collect`` account for every episode the rollout finishes and for the samples' explained
     variance in the same launch (``rr_rollout_collect_stats``; the rollout itself is bitwise
     unchanged): ``ro.stats.last()`` / ``ro.stats.window()`` return SB3's ``rollout/*`` figures and
-    ``train/explained_variance`` (``rollout_stats.RolloutStats``)."""
+    ``train/explained_variance`` (``rollout_stats.RolloutStats``).
+
+    A ``MlpCategoricalActorCritic`` (the reference's ``DiscreteActions3DOF`` stack, 3DOF batches
+    only): ``actions`` is [n_steps, N, 1], the chosen index as a float (SB3's buffer for a
+    ``Discrete`` space), and the env steps with the policy's table row. The fused path is the
+    two-launch one (``rr_policy_act_discrete`` + the env step, then ``rr_policy_bootstrap`` and
+    ``rr_gae``), so ``one_launch`` defaults to False; ``one_launch=True``, ``per_step=True``,
+    ``stats=True`` and a ``policy_dtype`` other than "fp32" raise. ``fused=False`` samples with
+    ``torch.multinomial`` on ``generator``."""
 
     def __init__(self, batch, policy, n_steps=16, gamma=0.99, gae_lambda=0.95, generator=None, fused=None,
                  seed=0, policy_dtype="fp32", one_launch=None, per_step=False, stats=False):
         self.env, self.policy = batch, policy
         self.n_steps, self.gamma, self.lam = n_steps, gamma, gae_lambda
         n, ns, na = batch.num_envs, batch.state_dim, batch.action_dim
+        self.discrete = isinstance(policy, MlpCategoricalActorCritic)
+        if self.discrete:  # refused before anything touches the device
+            if ns != 7 or na != 2:
+                raise ValueError("a Categorical policy drives the 3DOF env (its table rows are [gimbal, thrust]): "
+                                 "a 6DOF batch is refused")
+            what = ("one_launch=True" if one_launch else "per_step=True" if per_step else "stats=True" if stats
+                    else "policy_dtype=%r" % policy_dtype if policy_dtype != "fp32" else None)
+            if what:
+                raise ValueError("%s is not available for a Categorical policy: it collects with two launches per "
+                                 "step (rr_policy_act_discrete + the env step) on fp32 towers, and the one-launch "
+                                 "collect, rr_rollout_step and the collect statistics have no Categorical head" % what)
+            if fused and not fused_discrete_supported(policy, ns):
+                raise ValueError("the fused Categorical path needs 64x64 towers and 2 .. 4 choices")
+            if fused is None:
+                fused = fused_discrete_supported(policy, ns)
+            one_launch = False
         dev = batch.device
         f = dict(device=dev, dtype=torch.float32)
         self.obs = torch.zeros((n_steps, n, ns), **f)
-        self.actions = torch.zeros((n_steps, n, na), **f)
+        self.actions = torch.zeros((n_steps, n, 1 if self.discrete else na), **f)
         self.rewards = torch.zeros((n_steps, n), **f)
         self.starts = torch.zeros((n_steps, n), **f)   # SB3 episode_starts
         self.values = torch.zeros((n_steps, n), **f)
@@ -104,7 +130,7 @@ class DeviceRollout:
             from . import _lib
 
             self._lib = _lib.load()
-            self._pack = PolicyPack(policy, ns, na, dev, precision=policy_dtype)
+            self._pack = PolicyPack(policy, ns, policy.n_choices if self.discrete else na, dev, precision=policy_dtype)
             self.iter = torch.zeros((1,), dtype=torch.int64, device=dev)  # advanced by every collect (graph-safe)
             self.seed = int(seed) & (2 ** 64 - 1)
             self._ones = torch.ones((n,), dtype=torch.uint8, device=dev)
@@ -114,6 +140,8 @@ class DeviceRollout:
             from .batch import _ptr
 
             self._c, self._p = ctypes, _ptr
+            if self.discrete:  # the host table rr_policy_act_discrete copies into its launch
+                self._table = (ctypes.c_float * (2 * policy.n_choices))(*policy.table.reshape(-1).tolist())
             bufs = _lib.RrBuffers()
             _lib.check(self._lib.rr_get_buffers(batch._h, ctypes.byref(bufs)), "rr_get_buffers")
             self._term_obs = ctypes.c_void_p(bufs.terminal_obs)
@@ -131,14 +159,20 @@ class DeviceRollout:
         for t in range(self.n_steps):
             obs = self.last_obs
             mean, value = pol(obs)
-            noise = torch.randn(mean.shape, device=mean.device, generator=self.gen)
-            act = mean + pol.log_std.exp() * noise
+            if self.discrete:  # mean holds the logits; the env takes the table row of the drawn index
+                act = torch.multinomial(torch.softmax(mean, dim=-1), 1, generator=self.gen).to(mean.dtype)
+            else:
+                noise = torch.randn(mean.shape, device=mean.device, generator=self.gen)
+                act = mean + pol.log_std.exp() * noise
             self.obs[t].copy_(obs)
             self.actions[t].copy_(act)
             self.values[t].copy_(value)
             self.log_probs[t].copy_(pol.log_prob(mean, act))
             self.starts[t].copy_(self.last_start)
-            torch.clamp(act, -1.0, 1.0, out=self._clipped)
+            if self.discrete:
+                self._clipped.copy_(pol.continuous(act[:, 0]))
+            else:
+                torch.clamp(act, -1.0, 1.0, out=self._clipped)
             nobs, rew, done, trunc = env.step(self._clipped)
             # SB3 1.6: bootstrap timeouts with the value of the terminal observation
             env.copy_terminal(out=(self._tobs, None, None))
@@ -199,14 +233,21 @@ class DeviceRollout:
                                                p(self.last_value), stream), "rr_policy_bootstrap")
             self._finish(stream)
             return
+        if self.discrete:
+            na = 4  # the 4-head image (rr_policy_pack_discrete): rr_policy_bootstrap's (7, 4)
         for t in range(self.n_steps):
             prev = t > 0
-            _lib.check(lib.rr_policy_act(params, ns, na, prec, n, env.env_id_offset, obs, self.seed, it, t, p(self._clipped),
-                                         p(self.actions[t]), p(self.values[t]), p(self.log_probs[t]), p(self.obs[t]),
-                                         self._term_obs if prev else None, p(env.truncated) if prev else None,
-                                         p(env.reward) if prev else None, self.gamma,
-                                         p(self.rewards[t - 1]) if prev else None, done, p(self.starts[t]), stream),
-                       "rr_policy_act")
+            carry = (self._term_obs if prev else None, p(env.truncated) if prev else None,
+                     p(env.reward) if prev else None, self.gamma, p(self.rewards[t - 1]) if prev else None, done,
+                     p(self.starts[t]), stream)
+            out = (p(self._clipped), p(self.actions[t]), p(self.values[t]), p(self.log_probs[t]), p(self.obs[t]))
+            if self.discrete:
+                _lib.check(lib.rr_policy_act_discrete(params, ns, self.policy.n_choices, self._table, prec, n,
+                                                      env.env_id_offset, obs, self.seed, it, t, *out, *carry),
+                           "rr_policy_act_discrete")
+            else:
+                _lib.check(lib.rr_policy_act(params, ns, na, prec, n, env.env_id_offset, obs, self.seed, it, t, *out,
+                                             *carry), "rr_policy_act")
             env.step(self._clipped)
         _lib.check(lib.rr_policy_bootstrap(params, ns, na, prec, n, self._term_obs, p(env.truncated), p(env.reward),
                                            self.gamma, p(self.rewards[self.n_steps - 1]), obs, p(self.last_value),
