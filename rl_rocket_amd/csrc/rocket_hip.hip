@@ -401,6 +401,9 @@ int hip_fail(hipError_t e, const char* what)
     return fail(RR_EHIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// What entry points with a twin share. `who` names the entry point in the error text, built only on a refusal.
+int refuse(const char* who, const std::string& what) { return fail(RR_EINVAL, std::string(who) + ": " + what); }
+
 float ceil_f(double d)   // smallest float >= d
 {
     float f = (float)d;
@@ -1271,19 +1274,65 @@ static int policy_prec(const std::string& w, const float* params, int precision)
 #define RR_POL_UNSUPPORTED(fn) \
     fail(RR_EINVAL, fn ": supported (obs_dim, act_dim) are (14, 3) and (7, 2), precision RR_POLICY_FP32 / RR_POLICY_BF16 / RR_POLICY_FP16X3")
 
+// rr_policy_layout's 12 offsets of a pol::Layout into `off` (if given); the image's size in floats
+template <class LL>
+static int layout_offsets(int64_t* off)
+{
+    const int64_t v[12] = {LL::L1A, LL::B1, LL::L2A, LL::B2, LL::TOWER, LL::PI,
+                           LL::VF,  LL::HA, LL::HV,  LL::HB, LL::VB,    LL::LS};
+    for (int k = 0; off && k < 12; ++k) off[k] = v[k];
+    return LL::SIZE;
+}
+
+// The argument checks of rr_policy_act and rr_policy_act_discrete (`extra`: the latter's table)
+static int act_args_ok(const char* who, const float* params, const void* extra, const float* obs, const uint64_t* iter,
+                       const float* action_env, const float* action, const float* value, const float* log_prob,
+                       int64_t n, const float* prev_term_obs, const uint8_t* prev_truncated, const float* prev_reward,
+                       const float* reward_out, const uint8_t* done, const float* start_out)
+{
+    if (!params || !extra || !obs || !iter || !action_env || !action || !value || !log_prob || n <= 0)
+        return refuse(who, "null argument or n <= 0");
+    if (reward_out && (!prev_term_obs || !prev_truncated || !prev_reward))
+        return refuse(who, "reward_out needs prev_term_obs, prev_truncated, prev_reward");
+    if (start_out && !done) return refuse(who, "start_out needs done");
+    if (((uintptr_t)params & 15) != 0) return refuse(who, "params must be 16-B aligned");
+    return RR_OK;
+}
+
+// the noise key's seed words: splitmix64 of the user seed (raw seed words XORed into the key
+// made seed 1 give env e the stream seed 0 gives env e ^ 1, and seed 2^32 that of iteration + 1)
+static void act_seed_words(uint64_t seed, uint32_t& lo, uint32_t& hi)
+{
+    const uint64_t mixed = splitmix64(seed);
+    lo = (uint32_t)mixed;
+    hi = (uint32_t)(mixed >> 32);
+}
+
+// What the learner's host code knows of a policy shape: one tower's partial-gradient vector and packed image
+// in floats (ppo::Part / ppo::Pack), how many tensors a call binds, and their sizes in rr_policy_pack order
+struct LearnerShape {
+    int obs_dim;
+    int64_t part, pack;  // part == 0: not a supported shape
+    int n;
+    int64_t numel[13];
+    int64_t fin() const { return (part + kFinElems - 1) / kFinElems; }  // the finish kernel's blocks per tower
+};
+
+// The image <O, A> with `rows` action-head rows, `n` tensors bound (here: no template inside extern "C")
+template <int O, int A>
+static LearnerShape shape_of(int64_t rows, int n)
+{
+    return {O, ppo::Part<O, A>::SIZE, ppo::Pack<O, A>::SIZE, n,
+            {64 * O, 64, 64 * 64, 64, 64 * O, 64, 64 * 64, 64, 64 * rows, rows, 64, 1, rows}};
+}
+
 extern "C" {
 
 int rr_policy_layout(int obs_dim, int act_dim, int precision, int64_t* off)
 {
     int size = 0;
     const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto o, auto a, auto p) {
-        using LL = pol::Layout<decltype(o)::value, decltype(a)::value, decltype(p)::value>;
-        if (off) {
-            const int64_t v[12] = {LL::L1A, LL::B1, LL::L2A, LL::B2, LL::TOWER, LL::PI,
-                                   LL::VF,  LL::HA, LL::HV,  LL::HB, LL::VB,    LL::LS};
-            for (int k = 0; k < 12; ++k) off[k] = v[k];
-        }
-        size = LL::SIZE;
+        size = layout_offsets<pol::Layout<decltype(o)::value, decltype(a)::value, decltype(p)::value>>(off);
     });
     return ok ? size : RR_POL_UNSUPPORTED("rr_policy_layout");
 }
@@ -1313,18 +1362,14 @@ int rr_policy_act(const float* params, int obs_dim, int act_dim, int precision, 
                   const uint8_t* prev_truncated, const float* prev_reward, float gamma, float* reward_out,
                   const uint8_t* done, float* start_out, void* stream)
 {
-    if (!params || !obs || !iter || !action_env || !action || !value || !log_prob || n <= 0)
-        return fail(RR_EINVAL, "rr_policy_act: null argument or n <= 0");
-    if (reward_out && (!prev_term_obs || !prev_truncated || !prev_reward))
-        return fail(RR_EINVAL, "rr_policy_act: reward_out needs prev_term_obs, prev_truncated, prev_reward");
-    if (start_out && !done) return fail(RR_EINVAL, "rr_policy_act: start_out needs done");
-    if (((uintptr_t)params & 15) != 0) return fail(RR_EINVAL, "rr_policy_act: params must be 16-B aligned");
+    if (const int rc = act_args_ok("rr_policy_act", params, params, obs, iter, action_env, action, value, log_prob, n,
+                                   prev_term_obs, prev_truncated, prev_reward, reward_out, done, start_out);
+        rc != RR_OK)
+        return rc;
     const dim3 grid((unsigned)((n + pol::kEnvsPerBlock - 1) / pol::kEnvsPerBlock)), block(pol::kThreads);
     hipStream_t s = (hipStream_t)stream;
-    // the noise key's seed words: splitmix64 of the user seed (raw seed words XORed into the key
-    // made seed 1 give env e the stream seed 0 gives env e ^ 1, and seed 2^32 that of iteration + 1)
-    const uint64_t mixed = splitmix64(seed);
-    const uint32_t lo = (uint32_t)mixed, hi = (uint32_t)(mixed >> 32);
+    uint32_t lo, hi;
+    act_seed_words(seed, lo, hi);
     const bool ok = pol_dispatch(obs_dim, act_dim, precision, [&](auto o, auto a, auto p) {
         hipLaunchKernelGGL((policy_act_kernel<decltype(o)::value, decltype(a)::value, decltype(p)::value>), grid,
                            block, 0, s, params, n, env_id_offset, obs, lo, hi, iter, (uint32_t)t, action_env, action,
@@ -1637,16 +1682,11 @@ int64_t ppo_nwg(int64_t batch)
     return w < 1 ? 1 : (w > ppo::kMaxWG ? ppo::kMaxWG : w);
 }
 
-int64_t ppo_part_floats(int obs_dim, int act_dim)
+LearnerShape gauss_shape(int obs_dim, int act_dim)
 {
-    if (obs_dim == 14 && act_dim == 3) return ppo::Part<14, 3>::SIZE;
-    if (obs_dim == 7 && act_dim == 2) return ppo::Part<7, 2>::SIZE;
-    return 0;
-}
-
-int64_t ppo_pack_floats(int obs_dim, int act_dim)
-{
-    return obs_dim == 14 ? ppo::Pack<14, 3>::SIZE : ppo::Pack<7, 2>::SIZE;
+    if (obs_dim == 14 && act_dim == 3) return shape_of<14, 3>(3, 13);
+    if (obs_dim == 7 && act_dim == 2) return shape_of<7, 2>(2, 13);
+    return {};
 }
 
 // rr_ppo_workspace_size's layout: advantage partial sums | 2 packed tower images | 2 towers x nwg
@@ -1654,57 +1694,63 @@ int64_t ppo_pack_floats(int obs_dim, int act_dim)
 // for the next, chained one (the advantage sums, the packed images) sits ahead of the only section
 // whose size follows the call's batch: a chained call with a shorter minibatch, and so fewer
 // workgroups, finds both where the call before it wrote them.
-void ppo_carve(PpoLaunch& L, int obs_dim, int act_dim, int64_t batch, void* workspace)
+void ppo_carve(PpoLaunch& L, const LearnerShape& sh, int64_t batch, void* workspace)
 {
-    L.obs_dim = obs_dim;
+    L.obs_dim = sh.obs_dim;
     L.nwg = (int)ppo_nwg(batch);
     L.adv_part = (double*)workspace;
     L.pack = (float*)((char*)workspace + 2 * ppo::kAdvPart * sizeof(double));
-    L.part = L.pack + 2 * ppo_pack_floats(obs_dim, act_dim);
+    L.part = L.pack + 2 * sh.pack;
 }
+
+// The finish kernel's squared-gradient sums (two towers) and the step count, in floats, 16-B rows
+int64_t norm_floats(const LearnerShape& sh) { return (2 * sh.fin() + 1 + 3) / 4 * 4; }
 
 // rr_bc_update's workspace: 2 packed tower images | the finish's per-block sums and the step count,
 // 16-B rows | nwg partial-gradient vectors. What a call leaves for the chained one (the images) sits
 // ahead of the only section whose size follows the batch, as in ppo_carve.
-int64_t bc_fixed_floats(int obs_dim, int act_dim)
+int64_t bc_fixed_floats(const LearnerShape& sh) { return 2 * sh.pack + norm_floats(sh); }
+
+// rr_bc_update_workspace_size's bytes for a shape that passed
+int64_t bc_bytes(const LearnerShape& sh, int64_t batch)
 {
-    const int64_t fin = (ppo_part_floats(obs_dim, act_dim) + kFinElems - 1) / kFinElems;
-    return 2 * ppo_pack_floats(obs_dim, act_dim) + (2 * fin + 1 + 3) / 4 * 4;
+    int64_t floats = bc_fixed_floats(sh) + ppo_nwg(batch) * sh.part;
+#if defined(RR_DIAG_STAMPS)
+    // the shared gradient body writes its stamps past two towers' partial vectors: 16 floats per wave
+    floats += ppo_nwg(batch) * (sh.part + ppo::kWaves * 16);
+#endif
+    return floats * (int64_t)sizeof(float);
 }
 
-// What the learner entry points share. `who` names the entry point in the error text, built only on a refusal.
-int refuse(const char* who, const std::string& what) { return fail(RR_EINVAL, std::string(who) + ": " + what); }
-
 // The shape checks of the four *_workspace_size calls (sized: `bytes` is required too) and of rr_bc_update
-int learner_shape_ok(const char* who, int obs_dim, int act_dim, int64_t batch, const int64_t* bytes, bool sized = true)
+int learner_shape_ok(const char* who, const LearnerShape& sh, int64_t batch, const int64_t* bytes, bool sized = true)
 {
-    if (!ppo_part_floats(obs_dim, act_dim)) return refuse(who, "supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
+    if (!sh.part) return refuse(who, "supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
     if (batch < 2 || (sized && !bytes)) return refuse(who, sized ? "batch >= 2 and bytes required" : "batch >= 2 required");
     return RR_OK;
 }
 
 // rr_ppo_workspace_size's bytes for a shape that passed: ppo_carve's three sections
-int64_t ppo_bytes(int obs_dim, int act_dim, int64_t batch)
+int64_t ppo_bytes(const LearnerShape& sh, int64_t batch)
 {
-    const int64_t floats = ppo_nwg(batch) * ppo_part_floats(obs_dim, act_dim) + ppo_pack_floats(obs_dim, act_dim);
-    return (int64_t)(2 * ppo::kAdvPart * sizeof(double)) + 2 * floats * (int64_t)sizeof(float);
+    return (int64_t)(2 * ppo::kAdvPart * sizeof(double)) +
+           2 * (ppo_nwg(batch) * sh.part + sh.pack) * (int64_t)sizeof(float);
 }
 
-// rr_ppo_update_workspace_size's: + the finish kernel's squared-gradient sums (two towers) and the step count, 16-B rows
-int64_t ppo_update_bytes(int obs_dim, int act_dim, int64_t batch)
+// rr_ppo_update_workspace_size's: + the finish kernel's sums
+int64_t ppo_update_bytes(const LearnerShape& sh, int64_t batch)
 {
-    const int64_t fin = (ppo_part_floats(obs_dim, act_dim) + kFinElems - 1) / kFinElems;
-    return (ppo_bytes(obs_dim, act_dim, batch) + 15) / 16 * 16 + (2 * fin + 1 + 3) / 4 * 16;
+    return (ppo_bytes(sh, batch) + 15) / 16 * 16 + norm_floats(sh) * (int64_t)sizeof(float);
 }
 
-// The 13 policy tensors (rr_policy_pack order) into a launch record; false if one is null. With `a` also the
+// The shape's sh.n policy tensors (rr_policy_pack order) into a launch record; false if one is null. With `a` also the
 // optimizer launch's list: each tensor's Adam state and the prefix sums of the sizes (params are then writable)
-bool bind_policy(PolSrc& ps, PolGrad& pg, AdamList* a, int no, int na, const float* const* params, float* const* grads,
-                 float* const* exp_avg = nullptr, float* const* exp_avg_sq = nullptr, float* const* step = nullptr)
+bool bind_policy(PolSrc& ps, PolGrad& pg, AdamList* a, const LearnerShape& sh, const float* const* params,
+                 float* const* grads, float* const* exp_avg = nullptr, float* const* exp_avg_sq = nullptr,
+                 float* const* step = nullptr)
 {
-    const int64_t numel[13] = {64 * no, 64, 64 * 64, 64, 64 * no, 64, 64 * 64, 64, 64 * na, na, 64, 1, na};
-    if (a) a->n = 13;
-    for (int k = 0; k < 13; ++k) {
+    if (a) a->n = sh.n;
+    for (int k = 0; k < sh.n; ++k) {
         if (!params[k] || !grads[k] || (a && (!exp_avg[k] || !exp_avg_sq[k] || !step[k]))) return false;
         ps.p[k] = params[k];
         pg.p[k] = grads[k];
@@ -1714,8 +1760,8 @@ bool bind_policy(PolSrc& ps, PolGrad& pg, AdamList* a, int no, int na, const flo
         a->exp_avg[k] = exp_avg[k];
         a->exp_avg_sq[k] = exp_avg_sq[k];
         a->step[k] = step[k];
-        a->start[k + 1] = a->start[k] + numel[k];
-        a->wstart[k + 1] = a->wstart[k] + (numel[k] + kWave - 1) / kWave * kWave;
+        a->start[k + 1] = a->start[k] + sh.numel[k];
+        a->wstart[k + 1] = a->wstart[k] + (sh.numel[k] + kWave - 1) / kWave * kWave;
     }
     return true;
 }
@@ -1783,8 +1829,9 @@ int rr_clip_adam(int n_tensors, float* const* params, float* const* grads, float
 
 int rr_ppo_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
 {
-    const int rc = learner_shape_ok("rr_ppo_workspace_size", obs_dim, act_dim, batch, bytes);
-    if (rc == RR_OK) *bytes = ppo_bytes(obs_dim, act_dim, batch);
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
+    const int rc = learner_shape_ok("rr_ppo_workspace_size", sh, batch, bytes);
+    if (rc == RR_OK) *bytes = ppo_bytes(sh, batch);
     return rc;
 }
 
@@ -1800,11 +1847,12 @@ int rr_ppo_grad(int obs_dim, int act_dim, const float* const* params, float* con
     if (workspace_bytes < need) return fail(RR_EINVAL, "rr_ppo_grad: workspace smaller than rr_ppo_workspace_size");
     if (((uintptr_t)workspace & 15) != 0) return fail(RR_EINVAL, "rr_ppo_grad: workspace must be 16-B aligned");
     if (!(clip_range >= 0.0f)) return fail(RR_EINVAL, "rr_ppo_grad: clip_range must be >= 0");
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
     PpoLaunch L = {};
     L.op = 0;
-    if (!bind_policy(L.ps, L.pg, nullptr, obs_dim, act_dim, params, grads))
+    if (!bind_policy(L.ps, L.pg, nullptr, sh, params, grads))
         return fail(RR_EINVAL, "rr_ppo_grad: null parameter or gradient tensor");
-    ppo_carve(L, obs_dim, act_dim, batch, workspace);
+    ppo_carve(L, sh, batch, workspace);
     L.obs = obs;
     L.actions = actions;
     L.old_log_prob = old_log_prob;
@@ -1822,15 +1870,16 @@ int rr_ppo_grad(int obs_dim, int act_dim, const float* const* params, float* con
 
 int rr_ppo_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
 {
-    const int rc = learner_shape_ok("rr_ppo_update_workspace_size", obs_dim, act_dim, batch, bytes);
-    if (rc == RR_OK) *bytes = ppo_update_bytes(obs_dim, act_dim, batch);
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
+    const int rc = learner_shape_ok("rr_ppo_update_workspace_size", sh, batch, bytes);
+    if (rc == RR_OK) *bytes = ppo_update_bytes(sh, batch);
     return rc;
 }
 
 namespace {
-// rr_ppo_update's argument checks and launch record, for it and rr_ppo_update_opts (`who` names the
-// entry point in the error text, known_flags its flag bits; ws_need its workspace size)
-int ppo_update_record(const char* who, PpoLaunch& L, int obs_dim, int act_dim, float* const* params,
+// rr_ppo_update's argument checks and launch record, for it, rr_ppo_update_opts and rr_ppo_update_discrete
+// (`who` names the entry point in the error text, known_flags its flag bits; ws_need its workspace size)
+int ppo_update_record(const char* who, PpoLaunch& L, const LearnerShape& sh, float* const* params,
                       float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, float* const* step,
                       const float* obs, const float* actions, const float* old_log_prob, const float* advantages,
                       const float* returns, const int64_t* idx, int64_t batch, const int64_t* next_idx,
@@ -1847,11 +1896,11 @@ int ppo_update_record(const char* who, PpoLaunch& L, int obs_dim, int act_dim, f
     if (next_idx && !(next_batch >= 2 && next_batch <= batch)) return refuse(who, "next_batch must be in [2, batch]");
     L = {};
     L.op = 1;
-    if (!bind_policy(L.ps, L.pg, &L.a, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step))
+    if (!bind_policy(L.ps, L.pg, &L.a, sh, params, grads, exp_avg, exp_avg_sq, step))
         return refuse(who, "null parameter, gradient or optimizer-state tensor");
-    ppo_carve(L, obs_dim, act_dim, batch, workspace);
-    L.normw = (float*)((char*)workspace + (ppo_bytes(obs_dim, act_dim, batch) + 15) / 16 * 16);
-    L.nbp = (int)((L.a.wstart[13] + kAdamThreads - 1) / kAdamThreads);
+    ppo_carve(L, sh, batch, workspace);
+    L.normw = (float*)((char*)workspace + (ppo_bytes(sh, batch) + 15) / 16 * 16);
+    L.nbp = (int)((L.a.wstart[sh.n] + kAdamThreads - 1) / kAdamThreads);
     L.obs = obs;
     L.actions = actions;
     L.old_log_prob = old_log_prob;
@@ -1882,10 +1931,10 @@ int rr_ppo_update(int obs_dim, int act_dim, float* const* params, float* const* 
     int64_t need = 0;
     if (const int rc = rr_ppo_update_workspace_size(obs_dim, act_dim, batch, &need); rc != RR_OK) return rc;
     PpoLaunch L;
-    const int rc = ppo_update_record("rr_ppo_update", L, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step, obs,
-                                     actions, old_log_prob, advantages, returns, idx, batch, next_idx, next_batch, clip_range,
-                                     ent_coef, vf_coef, max_grad_norm, lr, beta1, beta2, eps, stats, flags, RR_PPO_CHAINED,
-                                     workspace, workspace_bytes, need);
+    const int rc = ppo_update_record("rr_ppo_update", L, gauss_shape(obs_dim, act_dim), params, grads, exp_avg,
+                                     exp_avg_sq, step, obs, actions, old_log_prob, advantages, returns, idx, batch,
+                                     next_idx, next_batch, clip_range, ent_coef, vf_coef, max_grad_norm, lr, beta1, beta2,
+                                     eps, stats, flags, RR_PPO_CHAINED, workspace, workspace_bytes, need);
     if (rc != RR_OK) return rc;
     const hipError_t err = (hipError_t)rrc_launch_learner(&L, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update: launch");
@@ -1901,9 +1950,10 @@ static_assert(ppo::kStop == RR_PPO_CTL_STOP && ppo::kDecide == RR_PPO_CTL_DECIDE
 
 int rr_ppo_update_opts_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
 {
-    const int rc = learner_shape_ok("rr_ppo_update_opts_workspace_size", obs_dim, act_dim, batch, bytes);
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
+    const int rc = learner_shape_ok("rr_ppo_update_opts_workspace_size", sh, batch, bytes);
     // + 8 floats: the call's statistics when the caller passes none (the control block sums them)
-    if (rc == RR_OK) *bytes = ppo_update_bytes(obs_dim, act_dim, batch) + 32;
+    if (rc == RR_OK) *bytes = ppo_update_bytes(sh, batch) + 32;
     return rc;
 }
 
@@ -1918,8 +1968,9 @@ int rr_ppo_update_opts(int obs_dim, int act_dim, float* const* params, float* co
 {
     int64_t need = 0;
     if (const int rc = rr_ppo_update_opts_workspace_size(obs_dim, act_dim, batch, &need); rc != RR_OK) return rc;
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
     PpoOptsLaunch O = {};
-    const int rc = ppo_update_record("rr_ppo_update_opts", O.base, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step,
+    const int rc = ppo_update_record("rr_ppo_update_opts", O.base, sh, params, grads, exp_avg, exp_avg_sq, step,
                                      obs, actions, old_log_prob, advantages, returns, idx, batch, next_idx, next_batch,
                                      clip_range, ent_coef, vf_coef, max_grad_norm, lr, beta1, beta2, eps, stats, flags,
                                      RR_PPO_CHAINED | RR_PPO_EPOCH_START, workspace, workspace_bytes, need);
@@ -1940,20 +1991,16 @@ int rr_ppo_update_opts(int obs_dim, int act_dim, float* const* params, float* co
     O.ctl.ctl = control;
     O.ctl.kl_limit = options->target_kl > 0.0f ? 1.5f * options->target_kl : HUGE_VALF;
     O.ctl.epoch_start = (flags & RR_PPO_EPOCH_START) != 0;
-    if (!stats) O.base.stats = (float*)((char*)workspace + ppo_update_bytes(obs_dim, act_dim, batch));
+    if (!stats) O.base.stats = (float*)((char*)workspace + ppo_update_bytes(sh, batch));
     const hipError_t err = (hipError_t)rrc_launch_learner_opts(&O, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_opts: launch");
 }
 
 int rr_bc_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
 {
-    if (const int rc = learner_shape_ok("rr_bc_update_workspace_size", obs_dim, act_dim, batch, bytes); rc != RR_OK) return rc;
-    const int64_t pf = ppo_part_floats(obs_dim, act_dim);
-    *bytes = (bc_fixed_floats(obs_dim, act_dim) + ppo_nwg(batch) * pf) * (int64_t)sizeof(float);
-#if defined(RR_DIAG_STAMPS)
-    // the shared gradient body writes its stamps past two towers' partial vectors: 16 floats per wave
-    *bytes += ppo_nwg(batch) * (pf + ppo::kWaves * 16) * (int64_t)sizeof(float);
-#endif
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
+    if (const int rc = learner_shape_ok("rr_bc_update_workspace_size", sh, batch, bytes); rc != RR_OK) return rc;
+    *bytes = bc_bytes(sh, batch);
     return RR_OK;
 }
 
@@ -1963,9 +2010,9 @@ int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* g
                  double beta1, double beta2, float eps, float* stats, uint32_t flags,
                  void* workspace, int64_t workspace_bytes, void* stream)
 {
-    int64_t need = 0;
-    if (const int rc = learner_shape_ok("rr_bc_update", obs_dim, act_dim, batch, nullptr, false); rc != RR_OK) return rc;
-    rr_bc_update_workspace_size(obs_dim, act_dim, batch, &need);
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
+    if (const int rc = learner_shape_ok("rr_bc_update", sh, batch, nullptr, false); rc != RR_OK) return rc;
+    const int64_t need = bc_bytes(sh, batch);
     if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !obs || !actions || !idx || !lr)
         return fail(RR_EINVAL, "rr_bc_update: null argument");
     const int rc = learner_ws_ok("rr_bc_update", workspace, workspace_bytes, need, flags, RR_BC_CHAINED);
@@ -1974,14 +2021,14 @@ int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* g
     if (!(ent_weight >= 0.0f)) return fail(RR_EINVAL, "rr_bc_update: ent_weight must be >= 0");
     if (!(l2_weight >= 0.0f)) return fail(RR_EINVAL, "rr_bc_update: l2_weight must be >= 0");
     BcLaunch L = {};
-    if (!bind_policy(L.ps, L.pg, &L.a, obs_dim, act_dim, params, grads, exp_avg, exp_avg_sq, step))
+    if (!bind_policy(L.ps, L.pg, &L.a, sh, params, grads, exp_avg, exp_avg_sq, step))
         return fail(RR_EINVAL, "rr_bc_update: null parameter, gradient or optimizer-state tensor");
     L.obs_dim = obs_dim;
     L.nwg = (int)ppo_nwg(batch);
     L.pack = (float*)workspace;
-    L.normw = L.pack + 2 * ppo_pack_floats(obs_dim, act_dim);
-    L.part = L.pack + bc_fixed_floats(obs_dim, act_dim);
-    L.nbp = (int)((L.a.wstart[13] + kAdamThreads - 1) / kAdamThreads);
+    L.normw = L.pack + 2 * sh.pack;
+    L.part = L.pack + bc_fixed_floats(sh);
+    L.nbp = (int)((L.a.wstart[sh.n] + kAdamThreads - 1) / kAdamThreads);
     L.obs = obs;
     L.actions = actions;
     L.idx = idx;
@@ -1997,9 +2044,6 @@ int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* g
 
 // ---- the Categorical policy (discrete/rocket_discrete.hip): obs_dim 7, 2 .. 4 choices on <7, 4> images ----
 namespace {
-using DiscPart = ppo::Part<7, 4>;
-using DiscPack = ppo::Pack<7, 4>;
-constexpr int64_t kDiscFin = (DiscPart::SIZE + kFinElems - 1) / kFinElems;
 constexpr int64_t kDiscSink = 64 * 4 + 4 + 4;  // floats: heads >= n_choices' weight and bias sums, log_std's slot
 
 int disc_shape_ok(const char* who, int obs_dim, int n_choices)
@@ -2009,25 +2053,14 @@ int disc_shape_ok(const char* who, int obs_dim, int n_choices)
     return RR_OK;
 }
 
-// rr_ppo_update's sections at <7, 4> (ppo_carve), then the finish's sums and the sink
-int64_t disc_grad_bytes(int64_t batch)
-{
-    return (int64_t)(2 * ppo::kAdvPart * sizeof(double)) +
-           2 * (ppo_nwg(batch) * DiscPart::SIZE + DiscPack::SIZE) * (int64_t)sizeof(float);
-}
-int64_t disc_norm_bytes() { return (2 * kDiscFin + 1 + 3) / 4 * 16; }
+// The <7, 4> image with n_choices action-head rows over the 12 tensors of a policy without a log_std
+LearnerShape disc_shape(int n_choices) { return shape_of<7, 4>(n_choices, 12); }
 }  // namespace
 
 int rr_policy_layout_discrete(int obs_dim, int64_t* off)
 {
     if (obs_dim != 7) return fail(RR_EINVAL, "rr_policy_layout_discrete: obs_dim must be 7 (the 3DOF env)");
-    using LL = pol::Layout<7, 4, 0>;
-    if (off) {
-        const int64_t v[12] = {LL::L1A, LL::B1, LL::L2A, LL::B2, LL::TOWER, LL::PI,
-                               LL::VF,  LL::HA, LL::HV,  LL::HB, LL::VB,    LL::LS};
-        for (int k = 0; k < 12; ++k) off[k] = v[k];
-    }
-    return LL::SIZE;
+    return layout_offsets<pol::Layout<7, 4, 0>>(off);
 }
 
 int rr_policy_pack_discrete(int obs_dim, int n_choices, const float* const* src, float* params, void* stream)
@@ -2056,12 +2089,10 @@ int rr_policy_act_discrete(const float* params, int obs_dim, int n_choices, cons
     const char* who = "rr_policy_act_discrete";
     if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
     if (precision != RR_POLICY_FP32) return refuse(who, "precision must be RR_POLICY_FP32");
-    if (!params || !table || !obs || !iter || !action_env || !action || !value || !log_prob || n <= 0)
-        return refuse(who, "null argument or n <= 0");
-    if (reward_out && (!prev_term_obs || !prev_truncated || !prev_reward))
-        return refuse(who, "reward_out needs prev_term_obs, prev_truncated, prev_reward");
-    if (start_out && !done) return refuse(who, "start_out needs done");
-    if (((uintptr_t)params & 15) != 0) return refuse(who, "params must be 16-B aligned");
+    if (const int rc = act_args_ok(who, params, table, obs, iter, action_env, action, value, log_prob, n, prev_term_obs,
+                                   prev_truncated, prev_reward, reward_out, done, start_out);
+        rc != RR_OK)
+        return rc;
     DiscreteLaunch D = {};
     D.op = kDiscAct;
     D.n_choices = n_choices;
@@ -2070,9 +2101,7 @@ int rr_policy_act_discrete(const float* params, int obs_dim, int n_choices, cons
             if (!std::isfinite(table[2 * k + c])) return refuse(who, "table entries must be finite");
             D.table[k][c] = table[2 * k + c];
         }
-    const uint64_t mixed = splitmix64(seed);  // as rr_policy_act: the same noise key
-    D.seed_lo = (uint32_t)mixed;
-    D.seed_hi = (uint32_t)(mixed >> 32);
+    act_seed_words(seed, D.seed_lo, D.seed_hi);  // as rr_policy_act: the same noise key
     D.params = params;
     D.n = n;
     D.id_off = env_id_offset;
@@ -2100,7 +2129,8 @@ int rr_ppo_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t ba
     const char* who = "rr_ppo_update_discrete_workspace_size";
     if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
     if (batch < 2 || !bytes) return refuse(who, "batch >= 2 and bytes required");
-    *bytes = (disc_grad_bytes(batch) + 15) / 16 * 16 + disc_norm_bytes() + kDiscSink * (int64_t)sizeof(float);
+    // rr_ppo_update's sections (ppo_carve, the finish's sums), then the sink
+    *bytes = ppo_update_bytes(disc_shape(n_choices), batch) + kDiscSink * (int64_t)sizeof(float);
     return RR_OK;
 }
 
@@ -2113,62 +2143,20 @@ int rr_ppo_update_discrete(int obs_dim, int n_choices, float* const* params, flo
                            void* workspace, int64_t workspace_bytes, void* stream)
 {
     const char* who = "rr_ppo_update_discrete";
-    int64_t need = 0;
-    if (const int rc = rr_ppo_update_discrete_workspace_size(obs_dim, n_choices, batch, &need); rc != RR_OK) {
-        if (obs_dim == 7 && n_choices >= 2 && n_choices <= 4) return refuse(who, "batch >= 2 required");
-        return disc_shape_ok(who, obs_dim, n_choices);
-    }
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !obs || !actions || !old_log_prob || !advantages ||
-        !returns || !idx || !lr)
-        return refuse(who, "null argument");
-    if (const int rc = learner_ws_ok(who, workspace, workspace_bytes, need, flags, RR_PPO_CHAINED); rc != RR_OK) return rc;
-    if (!(clip_range >= 0.0f)) return refuse(who, "clip_range must be >= 0");
-    if (next_idx && !(next_batch >= 2 && next_batch <= batch)) return refuse(who, "next_batch must be in [2, batch]");
+    if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
+    if (batch < 2) return refuse(who, "batch >= 2 required");
+    const LearnerShape sh = disc_shape(n_choices);
+    const int64_t sink_at = ppo_update_bytes(sh, batch);
     DiscreteLaunch D = {};
     D.op = kDiscUpdate;
     D.n_choices = n_choices;
-    PpoLaunch& L = D.u;
-    L.op = 1;
-    const int64_t numel[12] = {64 * 7, 64, 64 * 64, 64, 64 * 7, 64, 64 * 64, 64, 64 * n_choices, n_choices, 64, 1};
-    L.a.n = 12;
-    for (int k = 0; k < 12; ++k) {
-        if (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k] || !step[k])
-            return refuse(who, "null parameter, gradient or optimizer-state tensor");
-        L.ps.p[k] = params[k];
-        L.pg.p[k] = grads[k];
-        L.a.param[k] = params[k];
-        L.a.grad[k] = grads[k];
-        L.a.exp_avg[k] = exp_avg[k];
-        L.a.exp_avg_sq[k] = exp_avg_sq[k];
-        L.a.step[k] = step[k];
-        L.a.start[k + 1] = L.a.start[k] + numel[k];
-        L.a.wstart[k + 1] = L.a.wstart[k] + (numel[k] + kWave - 1) / kWave * kWave;
-    }
-    L.obs_dim = obs_dim;
-    L.nwg = (int)ppo_nwg(batch);
-    L.adv_part = (double*)workspace;
-    L.pack = (float*)((char*)workspace + 2 * ppo::kAdvPart * sizeof(double));
-    L.part = L.pack + 2 * DiscPack::SIZE;
-    L.normw = (float*)((char*)workspace + (disc_grad_bytes(batch) + 15) / 16 * 16);
-    D.sink = (float*)((char*)L.normw + disc_norm_bytes());
-    L.pg.p[12] = D.sink + 64 * 4 + 4;
-    L.nbp = (int)((L.a.wstart[12] + kAdamThreads - 1) / kAdamThreads);
-    L.obs = obs;
-    L.actions = actions;
-    L.old_log_prob = old_log_prob;
-    L.advantages = advantages;
-    L.returns = returns;
-    L.idx = idx;
-    L.next_idx = next_idx;
-    L.batch = batch;
-    L.next_batch = next_batch;
-    L.clip = clip_range;
-    L.ent = ent_coef;
-    L.vf = vf_coef;
-    L.max_norm = max_grad_norm;
-    set_adam(L, lr, beta1, beta2, eps);
-    L.stats = stats;
-    L.flags = flags & RR_PPO_CHAINED;
+    const int rc = ppo_update_record(who, D.u, sh, params, grads, exp_avg, exp_avg_sq, step, obs, actions, old_log_prob,
+                                     advantages, returns, idx, batch, next_idx, next_batch, clip_range, ent_coef, vf_coef,
+                                     max_grad_norm, lr, beta1, beta2, eps, stats, flags, RR_PPO_CHAINED, workspace,
+                                     workspace_bytes, sink_at + kDiscSink * (int64_t)sizeof(float));
+    if (rc != RR_OK) return rc;
+    D.sink = (float*)((char*)workspace + sink_at);
+    D.u.pg.p[12] = D.sink + 64 * 4 + 4;
     const hipError_t err = (hipError_t)rrc_launch_discrete(&D, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_discrete: launch");
 }

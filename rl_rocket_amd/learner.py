@@ -3,7 +3,11 @@
 ``ClipAdam``), the whole minibatch step as one library call (``PPOUpdate``) and an epoch of steps
 captured into a hipGraph (``GraphedPPOUpdate``). ``_AdamState`` is the binding of the 13 policy
 tensors and a capturable Adam's state that the fused calls share with ``bc.BCUpdate``.
-``PPOUpdateDiscrete`` is ``PPOUpdate`` for a ``MlpCategoricalActorCritic`` (``rr_ppo_update_discrete``).
+``PPOUpdate`` serves both distributions: for a ``MlpCategoricalActorCritic`` its constructor chooses
+``rr_ppo_update_discrete``, ``(ns, n_choices)`` as the shape, the actions as ``[n]`` indices and the
+policy's 12 tensors, and refuses the options; ``__call__`` is the same. ``PPOUpdateDiscrete`` is that
+path under its own name. ``ppo_update`` and ``GraphedPPOUpdate`` share their refusals
+(``_refuse_options``) and build the whole-minibatch step through ``_whole_step``.
 """
 import ctypes
 
@@ -118,28 +122,35 @@ class PPOGrad:
     (``tests/test_gpu_ppo.py``). Stream-ordered on the current stream; graph-capturable."""
 
     def __init__(self, policy, ro, batch_size, clip_range=0.2, ent_coef=0.01, vf_coef=0.5):
-        n = ro.n_steps * ro.env.num_envs
         ns, na = ro.env.state_dim, ro.env.action_dim
         if not fused_grad_supported(policy, ns, na):
             raise ValueError("PPOGrad needs an MlpActorCritic with 64x64 towers and (obs, act) in ((14, 3), (7, 2))")
+        dev = self._bind_rollout("rr_ppo_grad", policy, ro, batch_size, (ns, na), (na,), clip_range, ent_coef, vf_coef)
+        self.ws, self._nbytes = _workspace(self._lib, "rr_ppo_workspace_size", dev, ns, na, self.bs)
+        self._src = (ctypes.c_void_p * 13)(*[p.data_ptr() for p in self.params])
+        self._grads = [p.grad for p in self.params]
+        self._dst = (ctypes.c_void_p * 13)(*[g.data_ptr() for g in self._grads])
+
+    def _bind_rollout(self, who, policy, ro, batch_size, shape, act_shape, clip_range, ent_coef, vf_coef):
+        """What a learner call reads, for the library call ``who``: its shape arguments (``ns`` / ``na``), the
+        flattened rollout (actions as ``[n, *act_shape]``: ``[n, na]``, or ``[n]`` for indices), the policy's
+        tensors, the coefficients and ``stats``. Returns the rollout's device."""
+        n = ro.n_steps * ro.env.num_envs
         if not 2 <= batch_size <= n:
             raise ValueError("batch_size must be in [2, n_steps * num_envs]")
         self._lib = _lib.load()
-        self.ns, self.na, self.bs = ns, na, int(batch_size)
+        (self.ns, self.na), self.bs = shape, int(batch_size)
         self.coef = (float(clip_range), float(ent_coef), float(vf_coef))
         dev = ro.obs.device
-        self.data = [ro.obs.reshape(n, ns), ro.actions.reshape(n, na), ro.log_probs.reshape(n),
+        self.data = [ro.obs.reshape(n, self.ns), ro.actions.reshape(n, *act_shape), ro.log_probs.reshape(n),
                      ro.advantages.reshape(n), ro.returns.reshape(n)]
         for t in self.data:
             if not t.is_contiguous() or t.dtype != torch.float32:
                 raise ValueError("rollout tensors must be contiguous fp32")
         self.params = _policy_tensors(policy)
-        _check_params("rr_ppo_grad", self.params, dev, "rollout")
-        self.ws, self._nbytes = _workspace(self._lib, "rr_ppo_workspace_size", dev, ns, na, self.bs)
+        _check_params(who, self.params, dev, "rollout")
         self.stats = torch.zeros(5, dtype=torch.float32, device=dev)
-        self._src = (ctypes.c_void_p * 13)(*[p.data_ptr() for p in self.params])
-        self._grads = [p.grad for p in self.params]
-        self._dst = (ctypes.c_void_p * 13)(*[g.data_ptr() for g in self._grads])
+        return dev
 
     def __call__(self, idx):
         _check_idx(idx, self.bs, self.ws.device)
@@ -236,6 +247,18 @@ def _train_stats(ctl):
             "train/stop_epoch": int(ctl[L.RR_PPO_CTL_EPOCHS]) - 1 if stopped else None}
 
 
+_DISCRETE_FUSED = ("the fused Categorical learner (rr_ppo_update_discrete) is the one-replica call with a capturable "
+                   "torch.optim.Adam and SB3's defaults: %s needs fused=False (the autograd path takes it)")
+
+
+def _discrete_fused_ok(group, cvf, norm, tkl, train_stats=False):
+    """Refuses the arguments ``fused=True`` does not take for a Categorical policy, before any device work."""
+    what = ("group=" if group is not None else "clip_range_vf" if cvf else "normalize_advantage=False" if not norm
+            else "target_kl" if tkl else "train_stats" if train_stats else None)
+    if what:
+        raise ValueError(_DISCRETE_FUSED % what)
+
+
 class PPOUpdate(PPOGrad, _AdamState):
     """A whole PPO minibatch step — ``PPOGrad`` then ``ClipAdam``'s clip + Adam step on the same 13
     tensors — as ONE library call (``rr_ppo_update``). Without a gradient all_reduce between the
@@ -262,19 +285,33 @@ class PPOUpdate(PPOGrad, _AdamState):
       * ``train_stats()`` reads the block (one copy, which waits for the stream) and returns SB3's
         ``train/*`` means over the pass."""
 
+    _categorical = False  # PPOUpdateDiscrete: a Categorical policy only
+
     def __init__(self, policy, optimizer, ro, batch_size, clip_range=0.2, ent_coef=0.01, vf_coef=0.5,
                  max_grad_norm=0.5, clip_range_vf=None, normalize_advantage=True, target_kl=None, train_stats=False):
-        super().__init__(policy, ro, batch_size, clip_range, ent_coef, vf_coef)
+        who = type(self).__name__
         cvf, norm, tkl = _ppo_options(clip_range_vf, normalize_advantage, target_kl)
         self.opts = (_lib.RrPpoOptions(cvf, tkl, int(norm), int(bool(train_stats)))
                      if cvf or tkl or not norm or train_stats else None)
         if not clip_adam_supported(optimizer, list(policy.parameters())):
-            raise ValueError("PPOUpdate needs a capturable torch.optim.Adam over the policy's parameters "
-                             "(one group, no weight decay / amsgrad / maximize)")
+            raise ValueError("%s needs a capturable torch.optim.Adam over the policy's parameters "
+                             "(one group, no weight decay / amsgrad / maximize)" % who)
+        if self._categorical or isinstance(policy, MlpCategoricalActorCritic):
+            # what differs: the call, (ns, n_choices) as its shape, the actions as [n] indices, no options
+            ns = ro.env.state_dim
+            if not fused_discrete_supported(policy, ns):
+                raise ValueError("%s needs an MlpCategoricalActorCritic with 64x64 towers and 2 .. 4 "
+                                 "choices on a 3DOF rollout" % who)
+            _discrete_fused_ok(None, cvf, norm, tkl, train_stats)
+            self._call = "rr_ppo_update_discrete"
+            dev = self._bind_rollout(self._call, policy, ro, batch_size, (ns, policy.n_choices), (), clip_range,
+                                     ent_coef, vf_coef)
+        else:
+            self._call = "rr_ppo_update" if self.opts is None else "rr_ppo_update_opts"
+            super().__init__(policy, ro, batch_size, clip_range, ent_coef, vf_coef)
+            dev = self.ws.device
         self.max_norm = float(max_grad_norm) if max_grad_norm is not None else 0.0
-        dev = self.ws.device
         self._bind_adam(optimizer, self.params)
-        self._call = "rr_ppo_update" if self.opts is None else "rr_ppo_update_opts"
         self.ws, self._nbytes = _workspace(self._lib, self._call + "_workspace_size", dev, self.ns, self.na, self.bs)
         self._next = None
         self.ctl = self.old_values = None
@@ -282,6 +319,11 @@ class PPOUpdate(PPOGrad, _AdamState):
             self.ctl = torch.zeros(_lib.RR_PPO_CTL_SLOTS, dtype=torch.float32, device=dev)
             if cvf:
                 self.old_values = _old_values(ro, self.data[0].shape[0])
+        # the call's leading arguments, the same every time: the shape, the five pointer arrays, the rollout
+        # (rr_ppo_update_opts: old_values after it)
+        self._head = [self.ns, self.na, *self._ptrs, *[t.data_ptr() for t in self.data]]
+        if self.opts is not None:
+            self._head.append(None if self.old_values is None else self.old_values.data_ptr())
 
     def reset(self):
         """Clear the control block (stream-ordered, no wait): a new ``train()`` pass begins."""
@@ -302,89 +344,68 @@ class PPOUpdate(PPOGrad, _AdamState):
         if next_idx is not None and next_idx.numel() > idx.numel():
             raise ValueError("next_idx may not be longer than idx")
         if chained and self._next != (idx.data_ptr(), idx.numel()):
-            raise ValueError("chained=True needs the previous call on this PPOUpdate to have had next_idx=idx")
+            raise ValueError("chained=True needs the previous call on this %s to have had next_idx=idx"
+                             % type(self).__name__)
         nxt = None if next_idx is None else (next_idx.data_ptr(), next_idx.numel())
-        tensors = [self.ns, self.na, *self._ptrs, *[t.data_ptr() for t in self.data]]
         step = [idx.data_ptr(), idx.numel(), *(nxt or (None, 0)), *self.coef, self.max_norm, *self._adam_args()]
         flags = _lib.RR_PPO_CHAINED if chained else 0
         if self.opts is not None:  # rr_ppo_update's arguments with the options' among them
-            tensors.append(None if self.old_values is None else self.old_values.data_ptr())
             step += [ctypes.byref(self.opts), self.ctl.data_ptr()]
             flags |= _lib.RR_PPO_EPOCH_START if epoch_start else 0
-        _lib.check(getattr(self._lib, self._call)(*tensors, *step, self.stats.data_ptr(), flags, self.ws.data_ptr(),
+        _lib.check(getattr(self._lib, self._call)(*self._head, *step, self.stats.data_ptr(), flags, self.ws.data_ptr(),
                                                   self._nbytes, _stream(self.ws.device)), self._call)
         self._next = nxt  # (address, rows) of this call's next_idx: what chained=True may follow
         return self.stats
 
 
-_DISCRETE_FUSED = ("the fused Categorical learner (rr_ppo_update_discrete) is the one-replica call with a capturable "
-                   "torch.optim.Adam and SB3's defaults: %s needs fused=False (the autograd path takes it)")
+class PPOUpdateDiscrete(PPOUpdate):
+    """``PPOUpdate`` for a ``MlpCategoricalActorCritic`` on a 3DOF rollout, under the name and with the
+    constructor it had as a class of its own: one PPO minibatch step with a Categorical distribution as
+    ONE library call (``rr_ppo_update_discrete``: the learner's towers with a softmax head, the
+    entropy's gradient per sample, clip + Adam over the policy's 12 tensors). ``stats[2]`` is the
+    minibatch's mean entropy. SB3's defaults only: no ``clip_range_vf``, ``target_kl``, raw advantages
+    or control block (``opts`` is None)."""
 
-
-def _discrete_fused_ok(optimizer, policy, group, cvf, norm, tkl, train_stats=False):
-    """Refuses what ``fused=True`` does not take for a Categorical policy, before any device work."""
-    what = ("group=" if group is not None else "clip_range_vf" if cvf else "normalize_advantage=False" if not norm
-            else "target_kl" if tkl else "train_stats" if train_stats else None)
-    if what:
-        raise ValueError(_DISCRETE_FUSED % what)
-    if not clip_adam_supported(optimizer, list(policy.parameters())):
-        raise ValueError(_DISCRETE_FUSED % "another optimizer")
-
-
-class PPOUpdateDiscrete(_AdamState):
-    """``PPOUpdate`` for a ``MlpCategoricalActorCritic`` on a 3DOF rollout: one PPO minibatch step with a
-    Categorical distribution as ONE library call (``rr_ppo_update_discrete``: the learner's towers
-    with a softmax head, the entropy's gradient per sample, clip + Adam over the policy's 12
-    tensors). ``__call__(idx, next_idx=None, chained=False)`` and ``stats`` are ``PPOUpdate``'s;
-    ``stats[2]`` is the minibatch's mean entropy. SB3's defaults only: no ``clip_range_vf``,
-    ``target_kl``, raw advantages or control block (``opts`` is None)."""
-
-    opts = None
+    _categorical = True
 
     def __init__(self, policy, optimizer, ro, batch_size, clip_range=0.2, ent_coef=0.01, vf_coef=0.5,
                  max_grad_norm=0.5):
-        n = ro.n_steps * ro.env.num_envs
-        ns = ro.env.state_dim
-        if not fused_discrete_supported(policy, ns):
-            raise ValueError("PPOUpdateDiscrete needs an MlpCategoricalActorCritic with 64x64 towers and 2 .. 4 "
-                             "choices on a 3DOF rollout")
-        if not 2 <= batch_size <= n:
-            raise ValueError("batch_size must be in [2, n_steps * num_envs]")
-        if not clip_adam_supported(optimizer, list(policy.parameters())):
-            raise ValueError("PPOUpdateDiscrete needs a capturable torch.optim.Adam over the policy's parameters "
-                             "(one group, no weight decay / amsgrad / maximize)")
-        self._lib = _lib.load()
-        self.ns, self.na, self.bs = ns, policy.n_choices, int(batch_size)
-        self.coef = (float(clip_range), float(ent_coef), float(vf_coef))
-        self.max_norm = float(max_grad_norm) if max_grad_norm is not None else 0.0
-        dev = ro.obs.device
-        self.data = [ro.obs.reshape(n, ns), ro.actions.reshape(n), ro.log_probs.reshape(n),
-                     ro.advantages.reshape(n), ro.returns.reshape(n)]
-        for t in self.data:
-            if not t.is_contiguous() or t.dtype != torch.float32:
-                raise ValueError("rollout tensors must be contiguous fp32")
-        self.params = _policy_tensors(policy)
-        _check_params("rr_ppo_update_discrete", self.params, dev, "rollout")
-        self._bind_adam(optimizer, self.params)
-        self.ws, self._nbytes = _workspace(self._lib, "rr_ppo_update_discrete_workspace_size", dev, ns, self.na, self.bs)
-        self.stats = torch.zeros(5, dtype=torch.float32, device=dev)
-        self._next = None
+        super().__init__(policy, optimizer, ro, batch_size, clip_range, ent_coef, vf_coef, max_grad_norm)
 
-    def __call__(self, idx, next_idx=None, chained=False):
-        for t in (idx,) if next_idx is None else (idx, next_idx):
-            _check_idx(t, self.bs, self.ws.device, False, "idx / next_idx must be contiguous int64 device tensors")
-        if next_idx is not None and next_idx.numel() > idx.numel():
-            raise ValueError("next_idx may not be longer than idx")
-        if chained and self._next != (idx.data_ptr(), idx.numel()):
-            raise ValueError("chained=True needs the previous call on this PPOUpdateDiscrete to have had next_idx=idx")
-        nxt = None if next_idx is None else (next_idx.data_ptr(), next_idx.numel())
-        _lib.check(self._lib.rr_ppo_update_discrete(
-            self.ns, self.na, *self._ptrs, *[t.data_ptr() for t in self.data], idx.data_ptr(), idx.numel(),
-            *(nxt or (None, 0)), *self.coef, self.max_norm, *self._adam_args(), self.stats.data_ptr(),
-            _lib.RR_PPO_CHAINED if chained else 0, self.ws.data_ptr(), self._nbytes, _stream(self.ws.device)),
-            "rr_ppo_update_discrete")
-        self._next = nxt
-        return self.stats
+
+def _whole_step(policy, optimizer, ro, batch_size, *coef_and_options):
+    """The chained whole-minibatch call of the one-replica path (clip_range, ent_coef, vf_coef,
+    max_grad_norm, then ``PPOUpdate``'s options): ``PPOUpdateDiscrete`` for a Categorical policy,
+    whose options ``_refuse_options`` has refused by then."""
+    if isinstance(policy, MlpCategoricalActorCritic):
+        return PPOUpdateDiscrete(policy, optimizer, ro, batch_size, *coef_and_options[:4])
+    return PPOUpdate(policy, optimizer, ro, batch_size, *coef_and_options)
+
+
+def _refuse_options(policy, optimizer, group, fused, cvf, norm, tkl, train_stats=False, graphed=False):
+    """What ``ppo_update`` and ``GraphedPPOUpdate`` (``graphed``) refuse, before any device work. Returns
+    whether the step is the one-call path: fused, one replica, a capturable Adam."""
+    one_call = bool(fused) and group is None and clip_adam_supported(optimizer, list(policy.parameters()))
+    if fused and isinstance(policy, MlpCategoricalActorCritic):
+        _discrete_fused_ok(group, cvf, norm, tkl, train_stats)
+        if not one_call:
+            raise ValueError(_DISCRETE_FUSED % "another optimizer")
+    if tkl and group is not None:
+        raise ValueError("target_kl with a group is not supported: the ranks would stop at different minibatches")
+    if graphed and not one_call and (train_stats or tkl or (fused and (cvf or not norm))):
+        raise ValueError("clip_range_vf / normalize_advantage=False on the fused path, target_kl and train_stats "
+                         "need the fused one-replica update with a capturable torch.optim.Adam "
+                         "(rr_ppo_update_opts); fused=False takes clip_range_vf and normalize_advantage only")
+    if not graphed and fused and not one_call and (cvf or tkl or not norm):
+        raise ValueError("fused=True takes clip_range_vf / normalize_advantage=False / target_kl only on the "
+                         "one-replica path with a capturable torch.optim.Adam (rr_ppo_update_opts), not with a "
+                         "group or another optimizer")
+    return one_call
+
+
+def _loss_stats(st):
+    """A call's first three statistics under ``ppo_update``'s keys."""
+    return {"policy_loss": st[0], "value_loss": st[1], "entropy": st[2]}
 
 
 def _epoch_perms(n, n_epochs, dev, generator=None):
@@ -462,16 +483,7 @@ def ppo_update(policy, optimizer, ro, n_epochs=10, batch_size=65536, clip_range=
     ``clip_range_vf``, ``normalize_advantage=False`` and ``target_kl`` raise there."""
     n = ro.n_steps * ro.env.num_envs
     cvf, norm, tkl = _ppo_options(clip_range_vf, normalize_advantage, target_kl)
-    disc = isinstance(policy, MlpCategoricalActorCritic)
-    if fused and disc:
-        _discrete_fused_ok(optimizer, policy, group, cvf, norm, tkl)
-    if tkl and group is not None:
-        raise ValueError("target_kl with a group is not supported: the ranks would stop at different minibatches")
-    if fused and (cvf or tkl or not norm) and (group is not None
-                                               or not clip_adam_supported(optimizer, list(policy.parameters()))):
-        raise ValueError("fused=True takes clip_range_vf / normalize_advantage=False / target_kl only on the "
-                         "one-replica path with a capturable torch.optim.Adam (rr_ppo_update_opts), not with a "
-                         "group or another optimizer")
+    one_call = _refuse_options(policy, optimizer, group, fused, cvf, norm, tkl)
     if fused:
         perms = _epoch_perms(n, n_epochs, ro.obs.device, generator)
         if n % min(batch_size, n) == 1:
@@ -481,12 +493,10 @@ def ppo_update(policy, optimizer, ro, n_epochs=10, batch_size=65536, clip_range=
                              "needs >= 2 rows); choose another batch_size" % (n, batch_size))
         params = list(policy.parameters())
         stats = None
-        if group is None and clip_adam_supported(optimizer, params):
+        if one_call:
             # the whole minibatch step in one call, chained: each call sums the next one's statistics
-            step = (PPOUpdateDiscrete(policy, optimizer, ro, min(batch_size, n), clip_range, ent_coef, vf_coef,
-                                      max_grad_norm) if disc else
-                    PPOUpdate(policy, optimizer, ro, min(batch_size, n), clip_range, ent_coef, vf_coef, max_grad_norm,
-                              clip_range_vf, normalize_advantage, target_kl))
+            step = _whole_step(policy, optimizer, ro, min(batch_size, n), clip_range, ent_coef, vf_coef, max_grad_norm,
+                               clip_range_vf, normalize_advantage, target_kl)
             kw = {}
             for perm in perms:
                 for s in range(0, n, step.bs):
@@ -494,7 +504,7 @@ def ppo_update(policy, optimizer, ro, n_epochs=10, batch_size=65536, clip_range=
                     if step.opts is not None:
                         kw = dict(epoch_start=s == 0)
                     stats = step(perm[s:s + step.bs], nxt, chained=s > 0, **kw)
-            return {} if stats is None else dict(zip(("policy_loss", "value_loss", "entropy"), stats[:3].tolist()))
+            return {} if stats is None else _loss_stats(stats.tolist())
         grad = PPOGrad(policy, ro, min(batch_size, n), clip_range, ent_coef, vf_coef)
         adam = ClipAdam(optimizer, params, max_grad_norm) if clip_adam_supported(optimizer, params) else None
         for perm in perms:
@@ -507,7 +517,7 @@ def ppo_update(policy, optimizer, ro, n_epochs=10, batch_size=65536, clip_range=
                 else:
                     torch.nn.utils.clip_grad_norm_(params, max_grad_norm)
                     optimizer.step()
-        return {} if stats is None else dict(zip(("policy_loss", "value_loss", "entropy"), stats[:3].tolist()))
+        return {} if stats is None else _loss_stats(stats.tolist())
     obs = ro.obs.reshape(n, -1)
     act = ro.actions.reshape(n, -1)
     old_lp = ro.log_probs.reshape(n)
@@ -583,15 +593,14 @@ class GraphedPPOUpdate:
             raise ValueError("GraphedPPOUpdate needs an optimizer with capturable=True")
         cvf, norm, tkl = _ppo_options(clip_range_vf, normalize_advantage, target_kl)
         self._opt = (cvf, norm, tkl)
-        disc = isinstance(policy, MlpCategoricalActorCritic)
-        if fused is None and disc:
+        if fused is None and isinstance(policy, MlpCategoricalActorCritic):
             fused = (fused_discrete_supported(policy, ro.env.state_dim) and group is None
                      and not (cvf or tkl or not norm or train_stats)
                      and clip_adam_supported(optimizer, list(policy.parameters())))
-        if fused and disc:
-            _discrete_fused_ok(optimizer, policy, group, cvf, norm, tkl, train_stats)
-        if tkl and group is not None:
-            raise ValueError("target_kl with a group is not supported: the ranks would stop at different minibatches")
+        if fused is None:
+            fused = fused_grad_supported(policy, ro.env.state_dim, ro.env.action_dim)
+        self.fused = bool(fused)
+        one_call = _refuse_options(policy, optimizer, group, self.fused, cvf, norm, tkl, train_stats, graphed=True)
         n = ro.n_steps * ro.env.num_envs
         if n % batch_size:
             raise ValueError("n_steps * num_envs (%d) must be a multiple of batch_size (%d)" % (n, batch_size))
@@ -624,22 +633,11 @@ class GraphedPPOUpdate:
         self.params = params
         for p in params:
             p.grad = torch.zeros_like(p)
-        if fused is None:
-            fused = fused_grad_supported(policy, ro.env.state_dim, ro.env.action_dim)
-        self.fused = bool(fused)
-        one_call = self.fused and group is None and clip_adam_supported(optimizer, params)
-        if not one_call and (train_stats or tkl or (self.fused and (cvf or not norm))):
-            raise ValueError("clip_range_vf / normalize_advantage=False on the fused path, target_kl and train_stats "
-                             "need the fused one-replica update with a capturable torch.optim.Adam "
-                             "(rr_ppo_update_opts); fused=False takes clip_range_vf and normalize_advantage only")
         self.old_v = _old_values(ro, n) if cvf and not self.fused else None
         # fused, one replica, capturable Adam: the chained whole-minibatch call (rr_ppo_update, or
         # rr_ppo_update_opts with an option or train_stats)
-        self._update = (PPOUpdateDiscrete(policy, optimizer, ro, batch_size, clip_range, ent_coef, vf_coef, max_grad_norm)
-                        if one_call and disc else
-                        PPOUpdate(policy, optimizer, ro, batch_size, clip_range, ent_coef, vf_coef, max_grad_norm,
-                                  clip_range_vf, normalize_advantage, target_kl, train_stats)
-                        if one_call else None)
+        self._update = (_whole_step(policy, optimizer, ro, batch_size, clip_range, ent_coef, vf_coef, max_grad_norm,
+                                    clip_range_vf, normalize_advantage, target_kl, train_stats) if one_call else None)
         self._grad = (PPOGrad(policy, ro, batch_size, clip_range, ent_coef, vf_coef)
                       if self.fused and self._update is None else None)
         self._adam = (ClipAdam(optimizer, params, max_grad_norm)
@@ -678,22 +676,21 @@ class GraphedPPOUpdate:
     def _step(self, i, k=0):
         clip_range, ent_coef, vf_coef, max_grad_norm = self.coef
         pol = self.policy
-        if self._update is not None:
-            kw = dict(epoch_start=k == 0) if self._update.opts is not None else {}
-            st = self._update(i, self._mb(k + 1) if k + 1 < self.n_mb else None, chained=k > 0, **kw)
-            self._more = (st[3], st[4])
-            return {"policy_loss": st[0], "value_loss": st[1], "entropy": st[2]}
         if self.fused:
-            st = self._grad(i)
-            self._more = (st[3], st[4])
-            if self.group is not None:
-                _allreduce_grads(self.params, self.group)
-            if self._adam is not None:
-                self._adam()
+            if self._update is not None:
+                kw = dict(epoch_start=k == 0) if self._update.opts is not None else {}
+                st = self._update(i, self._mb(k + 1) if k + 1 < self.n_mb else None, chained=k > 0, **kw)
             else:
-                torch.nn.utils.clip_grad_norm_(self.params, max_grad_norm)
-                self.optimizer.step()
-            return {"policy_loss": st[0], "value_loss": st[1], "entropy": st[2]}
+                st = self._grad(i)
+                if self.group is not None:
+                    _allreduce_grads(self.params, self.group)
+                if self._adam is not None:
+                    self._adam()
+                else:
+                    torch.nn.utils.clip_grad_norm_(self.params, max_grad_norm)
+                    self.optimizer.step()
+            self._more = (st[3], st[4])
+            return _loss_stats(st)
         cvf, norm, _ = self._opt
         old = self.old_lp[i]
         loss, stats, lp, ratio = _ppo_loss(pol, self.obs[i], self.act[i], old, self.adv_all[i], self.ret[i],

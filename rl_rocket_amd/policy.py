@@ -6,7 +6,9 @@ separate pi / vf MLPs [64, 64] with tanh, diagonal Gaussian with state-independe
 log_std (init 0), orthogonal init (gain sqrt(2) hidden, 0.01 policy head, 1 value head).
 ``MlpCategoricalActorCritic`` is the policy SB3 builds behind the reference's ``DiscreteActions3DOF``
 (wrappers.py:24-35, a ``Discrete(K)`` action space): the same towers and initialisation, an action
-head of K logits, no log_std (SB3 ``CategoricalDistribution``).
+head of K logits, no log_std (SB3 ``CategoricalDistribution``). Both derive from ``_MlpTowers``, which
+builds and initialises the four nets and holds ``forward`` / ``value``; a class adds its distribution
+(``log_std``, or ``table`` and ``n_choices``) and ``log_prob`` / ``entropy``.
 """
 import math
 
@@ -52,8 +54,11 @@ class _Linear(nn.Linear):
         return _LinearFn.apply(x, self.weight, self.bias)
 
 
-class MlpActorCritic(nn.Module):
-    def __init__(self, obs_dim, act_dim, hidden=(64, 64), log_std_init=0.0):
+class _MlpTowers(nn.Module):
+    """What the two policies share: the pi / vf towers, ``action_net`` with ``out`` rows and ``value_net``,
+    initialised in this order (the draws of a seeded generator follow it), and the two forward passes."""
+
+    def __init__(self, obs_dim, out, hidden):
         super().__init__()
         self.hidden = tuple(hidden)
 
@@ -65,9 +70,8 @@ class MlpActorCritic(nn.Module):
             return nn.Sequential(*layers)
 
         self.pi_net, self.vf_net = mlp(), mlp()
-        self.action_net = _Linear(hidden[-1], act_dim)
+        self.action_net = _Linear(hidden[-1], out)
         self.value_net = _Linear(hidden[-1], 1)
-        self.log_std = nn.Parameter(torch.full((act_dim,), float(log_std_init)))
         for net in (self.pi_net, self.vf_net):
             for m in net:
                 if isinstance(m, nn.Linear):
@@ -83,6 +87,12 @@ class MlpActorCritic(nn.Module):
 
     def value(self, obs):
         return self.value_net(self.vf_net(obs)).squeeze(-1)
+
+
+class MlpActorCritic(_MlpTowers):
+    def __init__(self, obs_dim, act_dim, hidden=(64, 64), log_std_init=0.0):
+        super().__init__(obs_dim, act_dim, hidden)
+        self.log_std = nn.Parameter(torch.full((act_dim,), float(log_std_init)))
 
     def log_prob(self, mean, actions):
         std = self.log_std.exp()
@@ -93,8 +103,7 @@ class MlpActorCritic(nn.Module):
 
 
 
-
-class MlpCategoricalActorCritic(nn.Module):
+class MlpCategoricalActorCritic(_MlpTowers):
     """SB3 1.6 ``MlpPolicy`` over ``Discrete(n_choices)``: ``MlpActorCritic``'s towers and
     initialisation (``action_net`` gain 0.01), ``action_net`` giving ``n_choices`` logits, no
     ``log_std``. ``table`` ([n_choices][2], rows of [gimbal, thrust]) turns an index into the 3DOF
@@ -104,41 +113,14 @@ class MlpCategoricalActorCritic(nn.Module):
     log finite and its entropy term 0)."""
 
     def __init__(self, obs_dim, n_choices, table=DISCRETE_TABLE_3DOF, hidden=(64, 64)):
-        super().__init__()
-        self.hidden = tuple(hidden)
         table = torch.as_tensor(table, dtype=torch.float32)
         if table.dim() != 2 or table.shape != (n_choices, 2) or not bool(torch.isfinite(table).all()):
             raise ValueError("table must be [n_choices][2] finite numbers (rows of [gimbal, thrust])")
         if n_choices < 2:
             raise ValueError("n_choices must be at least 2")
+        super().__init__(obs_dim, int(n_choices), hidden)
         self.n_choices = int(n_choices)
         self.register_buffer("table", table.clone())
-
-        def mlp():
-            layers, d = [], obs_dim
-            for h in hidden:
-                layers += [_Linear(d, h), nn.Tanh()]
-                d = h
-            return nn.Sequential(*layers)
-
-        self.pi_net, self.vf_net = mlp(), mlp()
-        self.action_net = _Linear(hidden[-1], self.n_choices)
-        self.value_net = _Linear(hidden[-1], 1)
-        for net in (self.pi_net, self.vf_net):
-            for m in net:
-                if isinstance(m, nn.Linear):
-                    nn.init.orthogonal_(m.weight, gain=math.sqrt(2))
-                    nn.init.zeros_(m.bias)
-        nn.init.orthogonal_(self.action_net.weight, gain=0.01)
-        nn.init.zeros_(self.action_net.bias)
-        nn.init.orthogonal_(self.value_net.weight, gain=1.0)
-        nn.init.zeros_(self.value_net.bias)
-
-    def forward(self, obs):
-        return self.action_net(self.pi_net(obs)), self.value_net(self.vf_net(obs)).squeeze(-1)
-
-    def value(self, obs):
-        return self.value_net(self.vf_net(obs)).squeeze(-1)
 
     def log_prob(self, logits, actions):
         """log p of ``actions`` (indices as floats or integers, [...] or [..., 1]) under ``logits`` [..., K]."""
@@ -201,8 +183,10 @@ class PolicyPack:
             if act_dim != policy.n_choices:
                 raise ValueError("act_dim is the policy's n_choices for a Categorical policy")
             size = _lib.check(lib.rr_policy_layout_discrete(obs_dim, off), "rr_policy_layout_discrete")
+            self._pack = ("rr_policy_pack_discrete", (obs_dim, act_dim))
         else:
             size = _lib.check(lib.rr_policy_layout(obs_dim, act_dim, self.prec, off), "rr_policy_layout")
+            self._pack = ("rr_policy_pack", (obs_dim, act_dim, self.prec))  # pack()'s call and its shape arguments
         self.off = dict(zip(("L1A", "B1", "L2A", "B2", "TOWER", "PI", "VF", "HA", "HV", "HB", "VB", "LS"), list(off)))
         self.size, self.obs_dim, self.act_dim, self.policy = size, obs_dim, act_dim, policy
         self.buf = torch.zeros(size + 4, dtype=torch.float32, device=device)  # +4: 16-B alignment slack
@@ -301,13 +285,8 @@ class PolicyPack:
         ts = self._sources()
         src = (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.buf.device).cuda_stream)
-        if self.discrete:
-            _lib.check(_lib.load().rr_policy_pack_discrete(self.obs_dim, self.act_dim, src,
-                                                           ctypes.c_void_p(self.buf.data_ptr()), stream),
-                       "rr_policy_pack_discrete")
-            return self.buf
-        _lib.check(_lib.load().rr_policy_pack(self.obs_dim, self.act_dim, self.prec, src,
-                                              ctypes.c_void_p(self.buf.data_ptr()), stream), "rr_policy_pack")
+        call, shape = self._pack
+        _lib.check(getattr(_lib.load(), call)(*shape, src, ctypes.c_void_p(self.buf.data_ptr()), stream), call)
         return self.buf
 
     @torch.no_grad()
@@ -336,13 +315,10 @@ def _policy_tensors(policy):
     """The 13 parameter tensors in rr_policy_pack / rr_ppo_grad order (12 for a Categorical policy:
     there is no log_std)."""
     p = policy
-    if isinstance(p, MlpCategoricalActorCritic):
-        return [p.pi_net[0].weight, p.pi_net[0].bias, p.pi_net[2].weight, p.pi_net[2].bias,
-                p.vf_net[0].weight, p.vf_net[0].bias, p.vf_net[2].weight, p.vf_net[2].bias,
-                p.action_net.weight, p.action_net.bias, p.value_net.weight, p.value_net.bias]
-    return [p.pi_net[0].weight, p.pi_net[0].bias, p.pi_net[2].weight, p.pi_net[2].bias,
-            p.vf_net[0].weight, p.vf_net[0].bias, p.vf_net[2].weight, p.vf_net[2].bias,
-            p.action_net.weight, p.action_net.bias, p.value_net.weight, p.value_net.bias, p.log_std]
+    ts = [p.pi_net[0].weight, p.pi_net[0].bias, p.pi_net[2].weight, p.pi_net[2].bias,
+          p.vf_net[0].weight, p.vf_net[0].bias, p.vf_net[2].weight, p.vf_net[2].bias,
+          p.action_net.weight, p.action_net.bias, p.value_net.weight, p.value_net.bias]
+    return ts + [p.log_std] if hasattr(p, "log_std") else ts
 
 
 def fused_grad_supported(policy, obs_dim, act_dim):

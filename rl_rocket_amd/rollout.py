@@ -140,8 +140,12 @@ class DeviceRollout:
             from .batch import _ptr
 
             self._c, self._p = ctypes, _ptr
-            if self.discrete:  # the host table rr_policy_act_discrete copies into its launch
-                self._table = (ctypes.c_float * (2 * policy.n_choices))(*policy.table.reshape(-1).tolist())
+            # the two-launch path's act call (its symbol, the arguments between params and the precision)
+            # and rr_policy_bootstrap's act_dim
+            self._act, self._act_shape, self._boot_na = "rr_policy_act", (ns, na), na
+            if self.discrete:  # the host table rr_policy_act_discrete copies into its launch; the 4-head image's (7, 4)
+                table = (ctypes.c_float * (2 * policy.n_choices))(*policy.table.reshape(-1).tolist())
+                self._act, self._act_shape, self._boot_na = "rr_policy_act_discrete", (ns, policy.n_choices, table), 4
             bufs = _lib.RrBuffers()
             _lib.check(self._lib.rr_get_buffers(batch._h, ctypes.byref(bufs)), "rr_get_buffers")
             self._term_obs = ctypes.c_void_p(bufs.terminal_obs)
@@ -196,7 +200,7 @@ class DeviceRollout:
         env, lib, c, p = self.env, self._lib, self._c, self._p
         from . import _lib
 
-        n, ns, na = env.num_envs, env.state_dim, env.action_dim
+        n, ns, na = env.num_envs, env.state_dim, self._boot_na
         params = p(self._pack.pack())
         stream = c.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
         it, obs, done = p(self.iter), p(env.obs), p(env.done)
@@ -233,21 +237,15 @@ class DeviceRollout:
                                                p(self.last_value), stream), "rr_policy_bootstrap")
             self._finish(stream)
             return
-        if self.discrete:
-            na = 4  # the 4-head image (rr_policy_pack_discrete): rr_policy_bootstrap's (7, 4)
+        act = getattr(lib, self._act)
         for t in range(self.n_steps):
             prev = t > 0
             carry = (self._term_obs if prev else None, p(env.truncated) if prev else None,
                      p(env.reward) if prev else None, self.gamma, p(self.rewards[t - 1]) if prev else None, done,
                      p(self.starts[t]), stream)
             out = (p(self._clipped), p(self.actions[t]), p(self.values[t]), p(self.log_probs[t]), p(self.obs[t]))
-            if self.discrete:
-                _lib.check(lib.rr_policy_act_discrete(params, ns, self.policy.n_choices, self._table, prec, n,
-                                                      env.env_id_offset, obs, self.seed, it, t, *out, *carry),
-                           "rr_policy_act_discrete")
-            else:
-                _lib.check(lib.rr_policy_act(params, ns, na, prec, n, env.env_id_offset, obs, self.seed, it, t, *out,
-                                             *carry), "rr_policy_act")
+            _lib.check(act(params, *self._act_shape, prec, n, env.env_id_offset, obs, self.seed, it, t, *out, *carry),
+                       self._act)
             env.step(self._clipped)
         _lib.check(lib.rr_policy_bootstrap(params, ns, na, prec, n, self._term_obs, p(env.truncated), p(env.reward),
                                            self.gamma, p(self.rewards[self.n_steps - 1]), obs, p(self.last_value),

@@ -285,3 +285,31 @@ def test_fused_learner_calls_refuse_bad_arguments_and_keep_their_workspace_sizes
                 assert getattr(lib, size)(*shape, batch, ctypes.byref(ws)) == 0, (size, shape, batch)
                 got.append(ws.value)
             assert tuple(got) == expected, (size, shape, got)
+
+
+# The same four calls one row either side of a tile (64 / 65: one workgroup either way) and either side of
+# the first batch at which the workgroup count reaches its cap of 128 (tile 509 of 32 rows: 16 257).
+# Read from the build before the learner's host helpers took their sizes from one shape record.
+_WS_EDGE_BATCHES = (2, 64, 65, 16256, 16257, 16258)
+_WS_EDGE_BYTES = {
+    "rr_ppo_workspace_size": {(14, 3): (130720, 130720, 130720, 6594016, 6645312, 6645312),
+                              (7, 2): (126624, 126624, 126624, 6525408, 6576192, 6576192)},
+    "rr_ppo_update_workspace_size": {(14, 3): (132336, 132336, 132336, 6595632, 6646928, 6646928),
+                                     (7, 2): (128224, 128224, 128224, 6527008, 6577792, 6577792)},
+    "rr_ppo_update_opts_workspace_size": {(14, 3): (132368, 132368, 132368, 6595664, 6646960, 6646960),
+                                          (7, 2): (128256, 128256, 128256, 6527040, 6577824, 6577824)},
+    "rr_bc_update_workspace_size": {(14, 3): (102592, 102592, 102592, 3334240, 3359888, 3359888),
+                                    (7, 2): (98736, 98736, 98736, 3298128, 3323520, 3323520)},
+}
+
+
+def test_learner_workspace_sizes_at_the_tile_and_workgroup_cap_edges():
+    lib = _lib.load()
+    ws = ctypes.c_int64()
+    for size, table in _WS_EDGE_BYTES.items():
+        for shape, expected in table.items():
+            got = []
+            for batch in _WS_EDGE_BATCHES:
+                assert getattr(lib, size)(*shape, batch, ctypes.byref(ws)) == 0, (size, shape, batch)
+                got.append(ws.value)
+            assert tuple(got) == expected, (size, shape, got)

@@ -264,3 +264,66 @@ def test_c_abi_refuses_bad_arguments_before_any_hip_call():
     refused(update(clip=-0.1), who, "clip_range")
     refused(update(nxt=fake, next_batch=65), who, "next_batch")
     refused(update(nxt=fake, next_batch=1), who, "next_batch")
+
+
+# rr_ppo_update_discrete_workspace_size's bytes, read from the build in which it had size functions of its own:
+# one row either side of a tile (64 / 65) and either side of the first batch with 128 workgroups (16 257). The
+# <7, 4> image is sized whatever n_choices is.
+_WS_BATCHES = (2, 64, 65, 16256, 16257, 16258)
+_WS_BYTES = (131360, 131360, 131360, 6659168, 6710976, 6710976)
+
+
+@pytest.mark.parametrize("k", [2, 3, 4])
+def test_workspace_size_is_the_one_before_the_shared_shape_record(k):
+    lib = _lib.load()
+    ws = ctypes.c_int64()
+    got = []
+    for batch in _WS_BATCHES:
+        assert lib.rr_ppo_update_discrete_workspace_size(7, k, batch, ctypes.byref(ws)) == 0, (k, batch)
+        got.append(ws.value)
+    assert tuple(got) == _WS_BYTES, (k, got)
+
+
+# sha256[:16] over (key, bytes) of every state_dict entry in order, and the global generator's next draw, of the
+# policy classes as they were before they shared a base (seed, class, arguments)
+_INIT = {
+    (0, "MlpActorCritic", (14, 3)): ("ea58bb50846b9a93", 0.6514866352081299),
+    (0, "MlpActorCritic", (7, 2)): ("75b369ceab8e3071", 0.5089229941368103),
+    (0, "MlpCategoricalActorCritic", (7, 2)): ("b96ba1da2637977d", 0.5089229941368103),
+    (0, "MlpCategoricalActorCritic", (7, 3)): ("9b3e2f38197d14be", 0.5294811129570007),
+    (0, "MlpCategoricalActorCritic", (7, 4)): ("519aee89807598e0", 0.887469470500946),
+    (7, "MlpActorCritic", (14, 3)): ("0099244a820a3ccc", 0.1816447377204895),
+    (7, "MlpActorCritic", (7, 2)): ("392c9f5435f817cc", 0.1446022391319275),
+    (7, "MlpCategoricalActorCritic", (7, 2)): ("352e2db7795b165d", 0.1446022391319275),
+    (7, "MlpCategoricalActorCritic", (7, 3)): ("0652bf770afb4387", 0.7231861352920532),
+    (7, "MlpCategoricalActorCritic", (7, 4)): ("ce7811a7c3364d2b", 0.9301236271858215),
+}
+_NETS = ["pi_net.0.weight", "pi_net.0.bias", "pi_net.2.weight", "pi_net.2.bias", "vf_net.0.weight", "vf_net.0.bias",
+         "vf_net.2.weight", "vf_net.2.bias", "action_net.weight", "action_net.bias", "value_net.weight", "value_net.bias"]
+
+
+def test_both_policies_initialise_as_before_they_shared_a_base():
+    import hashlib
+
+    from rl_rocket_amd import rollout
+
+    for (seed, cls, args), (digest, draw) in _INIT.items():
+        torch.manual_seed(seed)
+        if cls == "MlpCategoricalActorCritic":
+            pol = rollout.MlpCategoricalActorCritic(*args, D.TABLES[args[1]])
+        else:
+            pol = rollout.MlpActorCritic(*args)
+        after = float(torch.rand(()))
+        sd = pol.state_dict()
+        h = hashlib.sha256()
+        for key, v in sd.items():
+            h.update(key.encode())
+            h.update(v.numpy().tobytes())
+        assert h.hexdigest()[:16] == digest and after == draw, (seed, cls, args, h.hexdigest()[:16], after)
+        gauss = cls == "MlpActorCritic"
+        assert list(sd) == (["log_std"] if gauss else ["table"]) + _NETS
+        named = dict(pol.named_parameters())
+        assert list(named) == (["log_std"] if gauss else []) + _NETS
+        ts = rollout._policy_tensors(pol)
+        assert len(ts) == (13 if gauss else 12)
+        assert all(t is named[n] for t, n in zip(ts, _NETS + ["log_std"]))

@@ -11,9 +11,9 @@ children with that tree as working directory:
             training iteration (ms)
   bc_ab     tools/bc_ab.py: the chained 65 536-row rr_bc_update / rr_ppo_update minibatch in a graph
             replay (us)
-  eager     this file with --child: PPOUpdate.__call__ and BCUpdate.__call__ called eagerly at batch
-            64, where the host path dominates: 7 runs of 2000 calls between two synchronises on the
-            host clock, the median run (us per call)
+  eager     this file with --child: PPOUpdate.__call__, BCUpdate.__call__ and PPOUpdateDiscrete.__call__
+            (3DOF, 4 choices) called eagerly at batch 64, where the host path dominates: 7 runs of
+            2000 calls between two synchronises on the host clock, the median run (us per call)
 The bar is the parent's own run-to-run spread (max - min over its rounds): this tree's median over
 the rounds may not lie above the parent's median by more than that. The record holds every raw
 number. A child that fails or exceeds its time limit ends the measurement.
@@ -32,13 +32,14 @@ BENCH = ["bench.py", "--gpus", "1", "--mode", "rollout", "--full", "--steps", "2
 
 
 def child():
-    """us per eager call of PPOUpdate and BCUpdate at batch 64, from the tree in the working directory."""
+    """us per eager call of PPOUpdate, BCUpdate and PPOUpdateDiscrete at batch 64, from the tree in the
+    working directory."""
     sys.path.insert(0, os.getcwd())
     import types
 
     import torch
     from rl_rocket_amd.bc import BCUpdate, Demonstrations
-    from rl_rocket_amd.rollout import MlpActorCritic, PPOUpdate
+    from rl_rocket_amd.rollout import MlpActorCritic, MlpCategoricalActorCritic, PPOUpdate, PPOUpdateDiscrete
 
     dev = torch.device("cuda", 0)
     m, bs, ns, na = 256, 64, 14, 3
@@ -50,11 +51,17 @@ def child():
                                obs=obs.view(1, m, ns), actions=acts.view(1, m, na), log_probs=torch.randn((1, m), **f),
                                advantages=torch.randn((1, m), **f), returns=torch.randn((1, m), **f))
     idx = torch.randperm(m, device=dev, generator=g)[:bs].contiguous()
+    # the Categorical arm: a 3DOF rollout whose actions are one of 4 indices, as floats
+    ro_d = types.SimpleNamespace(n_steps=1, env=types.SimpleNamespace(num_envs=m, state_dim=7, action_dim=2),
+                                 obs=obs[:, :7].contiguous().view(1, m, 7),
+                                 actions=torch.randint(0, 4, (1, m, 1), device=dev, generator=g).float(),
+                                 log_probs=ro.log_probs, advantages=ro.advantages, returns=ro.returns)
     out = {}
-    for name in ("ppo_update_call_us", "bc_update_call_us"):
-        pol = MlpActorCritic(ns, na).to(dev)
+    for name in ("ppo_update_call_us", "bc_update_call_us", "ppo_update_discrete_call_us"):
+        pol = (MlpCategoricalActorCritic(7, 4) if "discrete" in name else MlpActorCritic(ns, na)).to(dev)
         opt = torch.optim.Adam(pol.parameters(), lr=1e-4, capturable=True)
-        step = (PPOUpdate(pol, opt, ro, bs) if name.startswith("ppo") else
+        step = (PPOUpdateDiscrete(pol, opt, ro_d, bs) if "discrete" in name else
+                PPOUpdate(pol, opt, ro, bs) if name.startswith("ppo") else
                 BCUpdate(pol, opt, Demonstrations(obs, acts), bs))
         runs = []
         for _ in range(8):  # the first run warms up
@@ -88,6 +95,7 @@ def measure(tree):
             "bc_ab_bc_minibatch_us": a["bc"]["median"], "bc_ab_ppo_minibatch_us": a["ppo"]["median"],
             "eager_ppo_update_call_us": e["ppo_update_call_us"]["median"],
             "eager_bc_update_call_us": e["bc_update_call_us"]["median"],
+            "eager_ppo_update_discrete_call_us": e["ppo_update_discrete_call_us"]["median"],
             "raw": {"bench_ppo_update": upd, "bench_train_iteration": b["train_iteration"]["ms_per_iteration"],
                     "bc_ab": {k: a[k] for k in ("bc", "ppo")}, "eager": e}}
 
