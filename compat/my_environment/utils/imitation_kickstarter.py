@@ -2,7 +2,11 @@
 (``imitationKickstarter.train()`` pre-trains the policy on recorded ``(obs, action)`` pairs with
 ``imitation``'s ``bc.BC`` before PPO takes over) on ``rl_rocket_amd.bc.bc_train``: the same loss and
 ``imitation``'s defaults (minibatches of 32, Adam lr 1e-3, ``ent_weight`` 1e-3, ``l2_weight`` 0), on
-the device. ``policy`` is an ``rl_rocket_amd.rollout.MlpActorCritic``; neither ``imitation`` nor
+the device. ``policy`` is an ``rl_rocket_amd.rollout.MlpActorCritic``, or, for demonstrations flown
+through ``DiscreteActions3DOF`` (integer actions: indices into its table, from
+``RecordTrajectoryCallback`` tuples or from ``obs`` / ``actions`` arrays), an
+``rl_rocket_amd.rollout.MlpCategoricalActorCritic``, which is cloned on the indices (an action that is
+no integer in ``[0, n_choices)`` raises ``ValueError``); neither ``imitation`` nor
 stable-baselines3 is needed. ``play()`` (keyboard control under pygame) is out of scope like
 ``render()`` and raises.
 """

@@ -769,6 +769,36 @@ int rr_ppo_update_discrete(int obs_dim, int n_choices, float* const* params, flo
                            const float* lr, double beta1, double beta2, float eps, float* stats, uint32_t flags,
                            void* workspace, int64_t workspace_bytes, void* stream);
 
+/* rr_bc_update for this policy: one behaviour-cloning minibatch step on demonstrations obs [M][7] and
+ * actions [M], the demonstrated index as a float (what rr_policy_act_discrete writes and what the
+ * reference's RecordTrajectoryCallback records behind DiscreteActions3DOF), rows idx[0 .. batch):
+ * imitation's BehaviorCloningLossCalculator on SB3's CategoricalDistribution, loss.backward() and Adam's
+ * step, without gradient clipping:
+ *   log p_ik = z_ik - logsumexp_k z_ik,   logp_i = log p_{i, a_i}
+ *   H_i      = -sum_k p_ik log p_ik       (0 for a term whose p_ik is 0)
+ *   neglogp  = -mean_i logp_i,   entropy = mean_i H_i,   prob_true_act = mean_i exp(logp_i)
+ *   l2_norm  = 0.5 * sum over all 12 tensors of sum(w^2)
+ *   loss     = neglogp - ent_weight entropy + l2_weight l2_norm
+ *   d loss / d z_ik = -(1 / B) ((k == a_i) - p_ik) + ent_weight / B p_ik (log p_ik + H_i)
+ * The value tower and head receive the gradient l2_weight w only (zeros at l2_weight 0, written), and all
+ * 12 step tensors advance. The five tensor lists have 12 entries, in rr_ppo_update_discrete's order;
+ * stats is a device block of RR_BC_STAT_SLOTS floats (the slots above) or NULL. Four launches, three with
+ * flags & RR_BC_CHAINED (rr_bc_update's rule: the previous rr_bc_update_discrete on the same workspace
+ * was the last writer of the parameters). Capturable in a graph; deterministic (fixed-order sums, no
+ * atomics); lr is a device float.
+ * actions MUST hold integers in [0, n_choices): the call cannot check device data. It guarantees only
+ * that no address depends on them (an index is compared against k, never used as an offset); a row whose
+ * value names no choice contributes log p = 0 and a gradient that clones nothing.
+ * RR_EINVAL before any launch for obs_dim != 7, n_choices outside 2 .. 4, batch < 2, a null argument or
+ * tensor, a workspace too small or not 16-B aligned, NaN or negative ent_weight / l2_weight, unknown flag
+ * bits. workspace: rr_bc_update_discrete_workspace_size bytes. */
+int rr_bc_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes);
+int rr_bc_update_discrete(int obs_dim, int n_choices, float* const* params, float* const* grads,
+                          float* const* exp_avg, float* const* exp_avg_sq, float* const* step, const float* obs,
+                          const float* actions, const int64_t* idx, int64_t batch, float ent_weight, float l2_weight,
+                          const float* lr, double beta1, double beta2, float eps, float* stats, uint32_t flags,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

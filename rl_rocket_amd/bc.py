@@ -16,6 +16,19 @@ The loss is ``imitation``'s ``BehaviorCloningLossCalculator`` for a diagonal Gau
     l2_norm = 0.5 * sum over all parameter tensors of sum(w^2)
     loss    = neglogp - ent_weight * entropy + l2_weight * l2_norm
     prob_true_act = mean_i exp(logp_i)
+
+and for a ``MlpCategoricalActorCritic`` (the discrete 3DOF actions: the reference's keyboard demonstrations
+are indices into ``DiscreteActions3DOF``'s table) the same calculator on SB3's ``CategoricalDistribution``:
+
+    log p_ik = z_ik - logsumexp_k z_ik      logp_i = log p_{i, a_i}
+    H_i      = -sum_k p_ik log p_ik         (a term whose p_ik is 0 counts 0)
+    neglogp  = -mean_i logp_i               entropy = mean_i H_i
+    l2_norm  = 0.5 * sum over the 12 tensors of sum(w^2)
+    loss     = neglogp - ent_weight * entropy + l2_weight * l2_norm
+
+There ``acts`` is ``[M, 1]`` float32 holding the indices (the form of SB3's buffer and of
+``DeviceRollout.actions``), ``BCUpdate`` calls ``rr_bc_update_discrete`` on the policy's 12 tensors, and the
+indices are checked once (``_check_indices``) before anything indexes with them.
 """
 import math
 
@@ -25,14 +38,16 @@ import torch
 from . import _lib
 from .learner import (_AdamState, _allreduce_grads, _check_idx, _check_params, _epoch_perms, _stream, _workspace,
                       clip_adam_supported)
-from .policy import _policy_tensors, fused_grad_supported
+from .policy import MlpCategoricalActorCritic, _policy_tensors, fused_discrete_supported, fused_grad_supported
 
 STAT_NAMES = ("neglogp", "entropy", "ent_loss", "prob_true_act", "l2_norm", "l2_loss", "loss")  # RR_BC_STAT_*
 
 
 class Demonstrations:
     """``obs`` [M, ns] and ``acts`` [M, na]: contiguous float32 tensors on one device, row i a
-    normalised observation and the normalised action taken on it."""
+    normalised observation and the normalised action taken on it. For a Categorical policy ``acts`` is
+    [M, 1] and holds the chosen index as a float (``from_arrays`` on an integer array gives it, and
+    ``from_rollout`` on a Categorical collect is a view of the collect's buffers)."""
 
     def __init__(self, obs, acts):
         if obs.dim() != 2 or acts.dim() != 2 or obs.shape[0] != acts.shape[0]:
@@ -99,14 +114,32 @@ class Demonstrations:
         return cls(obs.contiguous(), trace.action[mask].contiguous())
 
 
+def _check_indices(acts, n_choices):
+    """One reduction on ``acts``' device: every demonstrated action of a Categorical policy is an integer
+    in ``[0, n_choices)`` in an ``[M, 1]`` tensor, or ``ValueError``. Nothing may index with them before this
+    (an index out of range in a ``gather`` on the GPU is a device-side assert), and the fused call, which
+    cannot check device data, is only given indices that passed."""
+    if acts.dim() != 2 or acts.shape[1] != 1:
+        raise ValueError("a Categorical policy's demonstrations are acts [M, 1] holding the chosen index, not %s"
+                         % (tuple(acts.shape),))
+    if not bool(((acts == acts.floor()) & (acts >= 0) & (acts < n_choices)).all()):  # NaN fails the first
+        raise ValueError("a Categorical policy's demonstrated actions must be integers in [0, %d)" % n_choices)
+
+
 def _bc_loss(policy, obs, acts, ent_weight, l2_weight):
-    """The loss of the module's head in PyTorch ops, with its seven figures (tensors)."""
-    mean = policy(obs)[0]
-    log_std = policy.log_std
-    std = log_std.exp()
-    logp = (-((acts - mean) ** 2) / (2 * std * std) - log_std - 0.5 * math.log(2 * math.pi)).sum(-1)
+    """The loss of the module's head in PyTorch ops, with its seven figures (tensors). A Categorical
+    policy's ``acts`` have passed ``_check_indices``."""
+    if isinstance(policy, MlpCategoricalActorCritic):
+        logits = policy(obs)[0]
+        logp = policy.log_prob(logits, acts)
+        entropy = policy.entropy(logits).mean()
+    else:
+        mean = policy(obs)[0]
+        log_std = policy.log_std
+        std = log_std.exp()
+        logp = (-((acts - mean) ** 2) / (2 * std * std) - log_std - 0.5 * math.log(2 * math.pi)).sum(-1)
+        entropy = (0.5 + 0.5 * math.log(2 * math.pi) + log_std).sum()
     neglogp = -logp.mean()
-    entropy = (0.5 + 0.5 * math.log(2 * math.pi) + log_std).sum()
     l2_norm = sum(p.square().sum() for p in policy.parameters()) / 2
     ent_loss, l2_loss = -ent_weight * entropy, l2_weight * l2_norm
     loss = neglogp + ent_loss + l2_loss
@@ -126,11 +159,23 @@ class BCUpdate(_AdamState):
     ``MlpActorCritic`` with 64x64 towers, a capturable Adam over exactly its parameters, and the
     gradient and state tensors kept (the library holds their addresses). ``lr`` is read from a device
     scalar that eager calls refresh; ``sync_lr()`` before replays of a captured graph.
-    ``last_stats()`` returns the seven figures as a dict (one copy, which waits for the stream)."""
+    ``last_stats()`` returns the seven figures as a dict (one copy, which waits for the stream).
+
+    An ``MlpCategoricalActorCritic`` (64x64 towers, 3DOF observations, 2 .. 4 choices) takes the same step
+    through ``rr_bc_update_discrete`` on its 12 tensors: ``demos.acts`` is [M, 1] indices, checked here once
+    (``ValueError`` for a value that is no integer in ``[0, n_choices)``); the entropy is the minibatch's
+    mean. Everything else, ``chained=`` included, is as above."""
 
     def __init__(self, policy, optimizer, demos, batch_size, ent_weight=1e-3, l2_weight=0.0):
         ns, na = demos.obs.shape[1], demos.acts.shape[1]
-        if not fused_grad_supported(policy, ns, na):
+        self._call = "rr_bc_update"
+        if isinstance(policy, MlpCategoricalActorCritic):
+            if not fused_discrete_supported(policy, ns):
+                raise ValueError("BCUpdate needs an MlpCategoricalActorCritic with 64x64 towers and 2 .. 4 choices "
+                                 "on 3DOF observations")
+            _check_indices(demos.acts, policy.n_choices)
+            self._call, na = "rr_bc_update_discrete", policy.n_choices  # the call's shape is (ns, n_choices)
+        elif not fused_grad_supported(policy, ns, na):
             raise ValueError("BCUpdate needs an MlpActorCritic with 64x64 towers and (obs, act) in ((14, 3), (7, 2))")
         if not 2 <= batch_size <= len(demos):
             raise ValueError("batch_size must be in [2, len(demos)]")
@@ -146,9 +191,9 @@ class BCUpdate(_AdamState):
         self.demos = demos
         dev = demos.device
         self.params = _policy_tensors(policy)
-        _check_params("rr_bc_update", self.params, dev, "demonstrations'")
+        _check_params(self._call, self.params, dev, "demonstrations'")
         self._bind_adam(optimizer, self.params)
-        self.ws, self._nbytes = _workspace(self._lib, "rr_bc_update_workspace_size", dev, ns, na, self.bs)
+        self.ws, self._nbytes = _workspace(self._lib, self._call + "_workspace_size", dev, ns, na, self.bs)
         self.stats = torch.zeros(_lib.RR_BC_STAT_SLOTS, dtype=torch.float32, device=dev)
         self._versions = None  # the parameters' version counters after the last call: what chained=True may follow
 
@@ -160,11 +205,11 @@ class BCUpdate(_AdamState):
         if chained and self._versions != [p._version for p in self.params]:
             raise ValueError("chained=True needs the previous call on this BCUpdate to be the last writer of the "
                              "parameters")
-        _lib.check(self._lib.rr_bc_update(
+        _lib.check(getattr(self._lib, self._call)(
             self.ns, self.na, *self._ptrs, self.demos.obs.data_ptr(), self.demos.acts.data_ptr(), idx.data_ptr(),
             idx.numel(), self.ent_weight, self.l2_weight, *self._adam_args(), self.stats.data_ptr(),
             _lib.RR_BC_CHAINED if chained else 0, self.ws.data_ptr(), self._nbytes, _stream(self.ws.device)),
-            "rr_bc_update")
+            self._call)
         self._versions = [p._version for p in self.params]
         return self.stats
 
@@ -180,7 +225,10 @@ def bc_train(policy, optimizer, demos, n_epochs=1, batch_size=None, generator=No
     ``fused=None`` takes ``BCUpdate`` (chained within the epoch) for an ``MlpActorCritic`` with 64x64
     towers on a GPU with a capturable Adam, and the same loss through PyTorch autograd otherwise
     (any policy whose ``policy(obs)[0]`` is the action mean and that has ``log_std``); ``fused=True``
-    insists, ``fused=False`` is the autograd path. A ``torch.distributed`` ``group`` averages the
+    insists, ``fused=False`` is the autograd path. An ``MlpCategoricalActorCritic`` is cloned on indices
+    (``acts`` [M, 1], checked once before anything indexes with them: ``ValueError``): the fused call is
+    ``rr_bc_update_discrete`` under the same conditions, the autograd path the loss through the policy's
+    ``log_prob`` / ``entropy`` on any device. A ``torch.distributed`` ``group`` averages the
     minibatch gradients over the ranks on the autograd path; the fused call has no gradient-only half
     and refuses it."""
     m = len(demos)
@@ -188,8 +236,12 @@ def bc_train(policy, optimizer, demos, n_epochs=1, batch_size=None, generator=No
     if not 1 <= bs <= m:
         raise ValueError("batch_size must be in [1, len(demos)]")
     params = list(policy.parameters())
-    can = (demos.obs.is_cuda and bs >= 2 and fused_grad_supported(policy, demos.obs.shape[1], demos.acts.shape[1])
-           and clip_adam_supported(optimizer, params))
+    if isinstance(policy, MlpCategoricalActorCritic):
+        _check_indices(demos.acts, policy.n_choices)
+        shape_ok = fused_discrete_supported(policy, demos.obs.shape[1])
+    else:
+        shape_ok = fused_grad_supported(policy, demos.obs.shape[1], demos.acts.shape[1])
+    can = demos.obs.is_cuda and bs >= 2 and shape_ok and clip_adam_supported(optimizer, params)
     if fused is None:
         fused = can and group is None
     if fused and group is not None:

@@ -47,6 +47,9 @@ SRC_BC = os.path.join(HERE, "csrc", "bc", "rocket_bc.hip")
 # act kernel's frame and the learner's pi tower with a softmax head, in a module of its own for the same
 # reason, with the learner's settings
 SRC_DISCRETE = os.path.join(HERE, "csrc", "discrete", "rocket_discrete.hip")
+# behaviour cloning of that policy (rr_bc_update_discrete): the behaviour-cloning unit's pipeline over the
+# discrete unit's images, in a module of its own for the same reason, with the learner's settings
+SRC_BC_DISCRETE = os.path.join(HERE, "csrc", "bc_discrete", "rocket_bc_discrete.hip")
 HEADER = os.path.join(ROOT, "include", "rocket_hip.h")
 OUT = os.path.join(HERE, "librocket_hip.so")
 # benchmark-only helper (not part of the product ABI): bench.py's event-timed direct-launch region
@@ -84,12 +87,12 @@ def command(resource_usage=False, out=OUT, defines=(), extra=(), src=SRC, compil
 def sources():
     """Every file the translation units are compiled from: all of csrc/, the recording and the
     exact-mode evaluation's translation units (which include only files of csrc/), the statistics
-    collect's unit with the .inc beside it, the learner-options, behaviour-cloning and discrete-action units and the
-    C-ABI header, sorted (tests/test_build_sources.py checks that the #include graph stays inside this list)."""
+    collect's unit with the .inc beside it, the learner-options, behaviour-cloning, discrete-action and
+    discrete behaviour-cloning units and the C-ABI header, sorted (tests/test_build_sources.py checks that the #include graph stays inside this list)."""
     csrc = os.path.join(HERE, "csrc")
     return sorted([os.path.join(csrc, f) for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))]
                   + [SRC_EVAL_TRACE, SRC_EVAL_EXACT, SRC_COLLECT_STATS, INC_COLLECT_STATS, SRC_PPO_OPTS, SRC_BC, SRC_DISCRETE,
-                     HEADER])
+                     SRC_BC_DISCRETE, HEADER])
 
 
 def source_hash():
@@ -111,7 +114,8 @@ def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
     """The six steps of the library build: the main, exact-mode, collect, recording-evaluation and
     exact-evaluation translation units compiled to objects (the latter four with EXACT_FLAGS /
     COLLECT_FLAGS / COLLECT_FLAGS / EVAL_EXACT_FLAGS); the last step compiles the learner-options, the
-    behaviour-cloning, the discrete-action and the statistics collect's units (all COLLECT_FLAGS, each a module of its own) and links them with
+    behaviour-cloning, the discrete-action, the discrete behaviour-cloning and the statistics collect's units
+    (all COLLECT_FLAGS, each a module of its own) and links them with
     those objects into `out` in one hipcc call. The flags of that call reach only the sources it
     compiles: the objects already hold their code objects."""
     o_main, o_exact, o_coll, o_trace = out + ".main.o", out + ".exact.o", out + ".collect.o", out + ".evaltrace.o"
@@ -126,7 +130,7 @@ def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
     c5 = command(resource_usage, o_evx, defines, list(extra) + EVAL_EXACT_FLAGS, SRC_EVAL_EXACT, compile_only=True,
                  preload=preload)
     objs = [o_main, o_exact, o_coll, o_trace, o_evx]
-    c6 = command(resource_usage, out, defines, list(extra) + COLLECT_FLAGS + objs + [SRC_PPO_OPTS, SRC_BC, SRC_DISCRETE],
+    c6 = command(resource_usage, out, defines, list(extra) + COLLECT_FLAGS + objs + [SRC_PPO_OPTS, SRC_BC, SRC_DISCRETE, SRC_BC_DISCRETE],
                  SRC_COLLECT_STATS,
                  preload=preload)
     return [c1, c2, c3, c4, c5, c6]

@@ -170,18 +170,8 @@ __global__ __launch_bounds__(256) void discrete_policy_pack_kernel(PolSrc src, i
     dst[k] = v;
 }
 
-// Element k of tower tw's learner image: ppo::pack_value, with zeros for the heads >= n_choices (the
-// tensors have n_choices rows) and for log_std's slots (there is none)
-template <int OBS, int ACT>
-__device__ __forceinline__ float discrete_pack_value(const PolSrc& src, int n_choices, int tw, int k)
-{
-    using K = ppo::Pack<OBS, ACT>;
-    if (k >= K::LS) return 0.0f;
-    if (tw == 0 && k >= K::HW && k < K::HB && (k - K::HW) / 64 >= n_choices) return 0.0f;
-    if (tw == 0 && k >= K::HB && k - K::HB >= n_choices) return 0.0f;
-    return ppo::pack_value<OBS, ACT>(src, tw, k);
-}
-
+// (discrete_pack_value, element k of a tower's learner image with zeros for the heads >= n_choices, is in
+// rocket_ppo.inc: bc_discrete/rocket_bc_discrete.hip packs with it too)
 template <int OBS, int ACT>
 __global__ __launch_bounds__(256) void discrete_prep_kernel(const float* __restrict__ adv,
                                                             const int64_t* __restrict__ idx, int64_t bs,

@@ -381,6 +381,7 @@ __attribute__((weak)) int rrc_launch_learner(const void*, void*) { return kNoUni
 __attribute__((weak)) int rrc_launch_learner_opts(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_bc(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_discrete(const void*, void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_bc_discrete(const void*, void*) { return kNoUnit; }
 }
 
 namespace {
@@ -2159,6 +2160,70 @@ int rr_ppo_update_discrete(int obs_dim, int n_choices, float* const* params, flo
     D.u.pg.p[12] = D.sink + 64 * 4 + 4;
     const hipError_t err = (hipError_t)rrc_launch_discrete(&D, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_discrete: launch");
+}
+
+namespace {
+// rr_bc_update_discrete's workspace: rr_bc_update's fixed sections over the <7, 4> image (2 packed tower
+// images | the finish's sums and the step count), the sink, then the nwg partial-gradient vectors: again
+// the only section whose size follows the batch is the last
+int64_t bc_disc_fixed_floats(const LearnerShape& sh) { return bc_fixed_floats(sh) + kDiscSink; }
+
+int64_t bc_disc_bytes(const LearnerShape& sh, int64_t batch)
+{
+    return bc_bytes(sh, batch) + kDiscSink * (int64_t)sizeof(float);
+}
+}  // namespace
+
+int rr_bc_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes)
+{
+    const char* who = "rr_bc_update_discrete_workspace_size";
+    if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
+    if (batch < 2 || !bytes) return refuse(who, "batch >= 2 and bytes required");
+    *bytes = bc_disc_bytes(disc_shape(n_choices), batch);
+    return RR_OK;
+}
+
+int rr_bc_update_discrete(int obs_dim, int n_choices, float* const* params, float* const* grads,
+                          float* const* exp_avg, float* const* exp_avg_sq, float* const* step, const float* obs,
+                          const float* actions, const int64_t* idx, int64_t batch, float ent_weight, float l2_weight,
+                          const float* lr, double beta1, double beta2, float eps, float* stats, uint32_t flags,
+                          void* workspace, int64_t workspace_bytes, void* stream)
+{
+    const char* who = "rr_bc_update_discrete";
+    if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
+    if (batch < 2) return refuse(who, "batch >= 2 required");
+    const LearnerShape sh = disc_shape(n_choices);
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !obs || !actions || !idx || !lr)
+        return refuse(who, "null argument");
+    const int rc = learner_ws_ok(who, workspace, workspace_bytes, bc_disc_bytes(sh, batch), flags, RR_BC_CHAINED);
+    if (rc != RR_OK) return rc;
+    // NaN fails the comparison too
+    if (!(ent_weight >= 0.0f)) return refuse(who, "ent_weight must be >= 0");
+    if (!(l2_weight >= 0.0f)) return refuse(who, "l2_weight must be >= 0");
+    BcDiscreteLaunch D = {};
+    BcLaunch& L = D.b;
+    if (!bind_policy(L.ps, L.pg, &L.a, sh, params, grads, exp_avg, exp_avg_sq, step))
+        return refuse(who, "null parameter, gradient or optimizer-state tensor");
+    D.n_choices = n_choices;
+    L.obs_dim = obs_dim;
+    L.nwg = (int)ppo_nwg(batch);
+    L.pack = (float*)workspace;
+    L.normw = L.pack + 2 * sh.pack;
+    D.sink = L.pack + bc_fixed_floats(sh);
+    L.pg.p[12] = D.sink + 64 * 4 + 4;  // log_std's slot of the finish body
+    L.part = L.pack + bc_disc_fixed_floats(sh);
+    L.nbp = (int)((L.a.wstart[sh.n] + kAdamThreads - 1) / kAdamThreads);
+    L.obs = obs;
+    L.actions = actions;
+    L.idx = idx;
+    L.batch = batch;
+    L.ent = ent_weight;
+    L.l2 = l2_weight;
+    set_adam(L, lr, beta1, beta2, eps);
+    L.stats = stats;
+    L.flags = flags;
+    const hipError_t err = (hipError_t)rrc_launch_bc_discrete(&D, stream);
+    return err == hipSuccess ? RR_OK : hip_fail(err, "rr_bc_update_discrete: launch");
 }
 
 }  // extern "C"

@@ -45,7 +45,9 @@
 // the finish and optimizer bodies as included text (rocket_ppo_finish_body.inc).
 // bc/rocket_bc.hip (rr_bc_update, behaviour cloning) instantiates the pi tower with LOSS 1 and
 // includes the same two bodies; discrete/rocket_discrete.hip (rr_ppo_update_discrete, the Categorical
-// policy) the pi tower with LOSS 2 over <7, 4> and the same two bodies.
+// policy) the pi tower with LOSS 2 over <7, 4> and the same two bodies; bc_discrete/rocket_bc_discrete.hip
+// (rr_bc_update_discrete, behaviour cloning of the Categorical policy) the pi tower with LOSS 3 over
+// <7, 4>, LOSS 2's head with LOSS 1's derivative, and the same two bodies.
 #pragma once
 
 #include <type_traits>
@@ -100,7 +102,7 @@ struct Part {
     static constexpr int HW = B2 + 64;          // [ACT][64 unit] (vf: row 0)
     static constexpr int HB = HW + 64 * ACT;    // [4]
     static constexpr int LS = HB + 4;           // [4] (pi)
-    static constexpr int ST = LS + 4;           // pi: pg sum, clip count, approx-kl sum (LOSS 2: + entropy sum); vf: squared-error sum
+    static constexpr int ST = LS + 4;           // pi: pg sum, clip count, approx-kl sum (LOSS 2: + entropy sum; LOSS 3: -logp, exp(logp), spare, entropy); vf: squared-error sum
     static constexpr int SIZE = ST + 4;
     static_assert(SIZE % 4 == 0, "16-B rows");
 };
@@ -223,6 +225,18 @@ __device__ __forceinline__ void adv_sums(const float* __restrict__ adv, const in
 // multiples of kAdvPart * 256; part[2 b] = sum, part[2 b + 1] = sum of squares); the blocks after
 // them the two towers' packed LDS images (pack[tower * Pack::SIZE + k], one element per thread),
 // which every gradient workgroup then stages with 16-B loads.
+// Element k of tower tw's learner image for the Categorical policy: ppo::pack_value, with zeros for the
+// heads >= n_choices (the tensors have n_choices rows) and for log_std's slots (there is none)
+template <int OBS, int ACT>
+__device__ __forceinline__ float discrete_pack_value(const PolSrc& src, int n_choices, int tw, int k)
+{
+    using K = ppo::Pack<OBS, ACT>;
+    if (k >= K::LS) return 0.0f;
+    if (tw == 0 && k >= K::HW && k < K::HB && (k - K::HW) / 64 >= n_choices) return 0.0f;
+    if (tw == 0 && k >= K::HB && k - K::HB >= n_choices) return 0.0f;
+    return ppo::pack_value<OBS, ACT>(src, tw, k);
+}
+
 template <int OBS, int ACT>
 __device__ __forceinline__ void ppo_prep_body(const float* __restrict__ adv, const int64_t* __restrict__ idx,
                                               int64_t bs, double* __restrict__ part, const PolSrc& src,
@@ -285,6 +299,11 @@ __global__ __launch_bounds__(256) void ppo_prep_kernel(const float* __restrict__
 // derivative here (ent_coef is an argument; the Gaussian kernels' finish adds theirs to log_std):
 //   dz_k = dlp ((k == a) - p_k) + ent_coef / B p_k (log p_k + H),   0 for k >= n_choices;
 // nothing goes to the log_std sums, and a fourth per-sample sum carries H.
+// LOSS 3 (behaviour cloning of the Categorical policy, bc_discrete/rocket_bc_discrete.hip; pi tower over
+// <OBS, 4>, NORM false): LOSS 2's softmax and entropy lines with LOSS 1's dlp = -1 / B and ent_coef the
+// cloning loss's ent_weight:
+//   dz_k = -(1 / B) ((k == a) - p_k) + ent_weight / B p_k (log p_k + H),   0 for k >= n_choices;
+// no ratio, no clip; old_lp / adv are not read. The four sums are -log_prob, exp(log_prob), a spare and H.
 template <int OBS, int ACT, int TW, bool VCLIP = false, bool NORM = true, int LOSS = 0>
 __device__ __forceinline__ void ppo_grad_tower(
     float* __restrict__ lds, const float* __restrict__ obs, const float* __restrict__ act,
@@ -300,6 +319,8 @@ __device__ __forceinline__ void ppo_grad_tower(
     constexpr int KP1 = L::KP1;
     constexpr int TS = ppo::kTS;
     constexpr int tw = TW;
+    constexpr bool CAT = LOSS == 2 || LOSS == 3;    // the softmax head
+    constexpr bool CLONE = LOSS == 1 || LOSS == 3;  // d loss / d log_prob = -1 / B: no ratio
     const int lane = threadIdx.x & (kWave - 1), half = lane >> 5, j = lane & 31;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     float* sp = lds;
@@ -329,13 +350,13 @@ __device__ __forceinline__ void ppo_grad_tower(
             in.x[k] = col < OBS ? obs[r * OBS + col] : 0.0f;
         }
         if (tw == 0) {
-            if constexpr (LOSS == 2) {
+            if constexpr (CAT) {
                 in.a[0] = act[r];  // the chosen index
             } else {
 #pragma unroll
                 for (int a = 0; a < ACT; ++a) in.a[a] = act[r * ACT + a];
             }
-            if constexpr (LOSS != 1) {
+            if constexpr (!CLONE) {
                 in.olp = old_lp[r];
                 in.av = adv[r];
             }
@@ -403,7 +424,7 @@ __device__ __forceinline__ void ppo_grad_tower(
         for (int r = 0; r < 16; ++r) accW1[b][r] = 0.0f;
     float hw_acc[ACT], hb_acc[ACT], ls_acc[ACT], b2_acc = 0.0f;
     float st0 = 0.0f, st1 = 0.0f, st2 = 0.0f;
-    [[maybe_unused]] float st3 = 0.0f;  // LOSS 2: the entropy sum
+    [[maybe_unused]] float st3 = 0.0f;  // LOSS 2 / 3: the entropy sum
 #pragma unroll
     for (int a = 0; a < ACT; ++a) hw_acc[a] = hb_acc[a] = ls_acc[a] = 0.0f;
     float ls[ACT], var[ACT];
@@ -439,12 +460,12 @@ __device__ __forceinline__ void ppo_grad_tower(
         float dh[ACT];
         if (tw == 0) {
             float A;
-            if constexpr (LOSS == 1) A = 0.0f;  // no advantages
+            if constexpr (CLONE) A = 0.0f;  // no advantages
             else if constexpr (NORM) A = valid ? ((in.av - a_mean) - a_mean_lo) / a_den : 0.0f;
             else A = valid ? in.av : 0.0f;
             float lp = 0.0f, d[ACT];
             [[maybe_unused]] float pr[ACT], lpk[ACT], H = 0.0f;
-            if constexpr (LOSS == 2) {
+            if constexpr (CAT) {
                 // softmax over the first n_choices logits: log p_k from the log of the sum, so that a
                 // p_k that underflows to 0 leaves log p_k finite
                 float z[ACT];
@@ -479,7 +500,7 @@ __device__ __forceinline__ void ppo_grad_tower(
             }
             // d loss / d lp; PPO's ratio terms are read again by its sums below
             float dlp, lr, r, u, c;
-            if constexpr (LOSS == 1) {
+            if constexpr (CLONE) {
                 dlp = valid ? -inv_b : 0.0f;
             } else {
                 lr = lp - in.olp;
@@ -491,7 +512,7 @@ __device__ __forceinline__ void ppo_grad_tower(
                 const float mask = (r >= lo && r <= hi) ? 1.0f : 0.0f;
                 dlp = valid ? -inv_b * (A * gu + A * gc * mask) * r : 0.0f;
             }
-            if constexpr (LOSS == 2) {
+            if constexpr (CAT) {
                 // d lp / d z_k = (k == a) - p_k; d(-H) / d z_k = p_k (log p_k + H)
                 const float ec = valid ? ent_coef * inv_b : 0.0f;
 #pragma unroll
@@ -512,9 +533,10 @@ __device__ __forceinline__ void ppo_grad_tower(
                 }
             }
             if (half == 0 && valid) {
-                if constexpr (LOSS == 1) {
+                if constexpr (CLONE) {
                     st0 -= lp;
                     st1 += expf(lp);
+                    if constexpr (LOSS == 3) st3 += H;
                 } else {
                     st0 -= fminf(u, c);
                     st1 += fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
@@ -694,7 +716,7 @@ __device__ __forceinline__ void ppo_grad_tower(
     st0 = ppo::wave_sum(st0);
     st1 = ppo::wave_sum(st1);
     st2 = ppo::wave_sum(st2);
-    if constexpr (LOSS == 2) st3 = ppo::wave_sum(st3);
+    if constexpr (CAT) st3 = ppo::wave_sum(st3);
     __syncthreads();  // every wave is done with its tiles: LDS becomes the reduction buffer
     float* red = lds + wv * PT::SIZE;
 #pragma unroll
@@ -718,7 +740,7 @@ __device__ __forceinline__ void ppo_grad_tower(
             }
         red[PT::HB + lane] = hb;
         red[PT::LS + lane] = l;
-        red[PT::ST + lane] = lane == 0 ? st0 : lane == 1 ? st1 : lane == 2 ? st2 : (LOSS == 2 ? st3 : 0.0f);
+        red[PT::ST + lane] = lane == 0 ? st0 : lane == 1 ? st1 : lane == 2 ? st2 : (CAT ? st3 : 0.0f);
     }
     __syncthreads();
     // the four waves' vectors summed as 16-B rows (PT::SIZE % 4 == 0: every row 16-B aligned)
@@ -899,6 +921,16 @@ struct DiscreteLaunch {
     float gamma;
 };
 static_assert(std::is_trivially_copyable_v<DiscreteLaunch>, "DiscreteLaunch crosses TUs by memcpy");
+
+// rr_bc_update_discrete's launches (bc_discrete/rocket_bc_discrete.hip, rrc_launch_bc_discrete): an
+// rr_bc_update record over 12 tensors whose pg.p[12] is four spare floats of the workspace, the number of
+// choices, and `sink`, 260 floats (where the finish puts the zero sums of heads >= n_choices)
+struct BcDiscreteLaunch {
+    BcLaunch b;
+    int n_choices;
+    float* sink;
+};
+static_assert(std::is_trivially_copyable_v<BcDiscreteLaunch>, "BcDiscreteLaunch crosses TUs by memcpy");
 
 // Element k of policy tensor t (rr_ppo_grad order) into the packed images (two towers of Pack::SIZE).
 template <int OBS, int ACT>

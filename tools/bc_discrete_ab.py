@@ -1,0 +1,148 @@
+#!/usr/bin/env python
+"""What a behaviour-cloning minibatch of the Categorical policy costs on the device
+(rr_bc_update_discrete) beside the Gaussian policy's (rr_bc_update at (7, 2)), beside a PPO minibatch of
+the same policy (rr_ppo_update_discrete) and beside the same loss in PyTorch autograd. HIP events, one
+JSON record.
+
+    python tools/bc_discrete_ab.py [--rows 1048576] [--batch 65536] [--runs 7] [--replays 10] [--out FILE]
+
+3DOF shapes (7 observations), K = 4 choices, fp32, synthetic rows (the kernels' time does not depend on
+the values; the indices are valid), one permutation cut into rows / batch minibatches. Four arms on
+copies of one policy (the Gaussian arm on an MlpActorCritic(7, 2) and the same observations):
+  bc_discrete   rows / batch CHAINED rr_bc_update_discrete calls captured in one graph (an eager call
+                before the capture leaves the packed image the first one uses): 3 launches per minibatch
+  bc_gauss      the same for rr_bc_update at (7, 2)
+  ppo_discrete  the same for rr_ppo_update_discrete with its defaults, each call handing the next one its
+                advantage statistics: 3 launches per minibatch, two towers on separate workgroups
+  autograd      the same minibatches through bc_train's PyTorch path for the Categorical policy (index,
+                forward, loss, backward, Adam(capturable).step()), eager, one synchronise at the end
+A run times `--replays` graph replays (the three fused arms) or one pass over the minibatches (autograd)
+between two events and reports us per minibatch; the runs alternate between the arms in one session,
+`--runs` of each. The record holds every run, the medians and each arm's spread (max - min).
+"""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+import types
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1048576)
+    ap.add_argument("--batch", type=int, default=65536)
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--replays", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import torch
+    from rl_rocket_amd import _lib, build
+    from rl_rocket_amd.bc import BCUpdate, Demonstrations, _bc_loss
+    from rl_rocket_amd.rollout import MlpActorCritic, MlpCategoricalActorCritic, PPOUpdate
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bc_discrete_ab.py measures on the GPU; no HIP device found")
+    dev = torch.device("cuda", 0)
+    m, bs, ns, k = args.rows, args.batch, 7, 4
+    if m % bs or m // bs < 2:
+        raise SystemExit("--rows must be a multiple (>= 2) of --batch")
+    g = torch.Generator(dev).manual_seed(0)
+    f = dict(device=dev, dtype=torch.float32, generator=g)
+    torch.manual_seed(0)
+    pol = MlpCategoricalActorCritic(ns, k).to(dev)
+    gauss = MlpActorCritic(ns, 2).to(dev)
+    obs = 0.7 * torch.randn((m, ns), **f)
+    index = torch.randint(0, k, (m, 1), device=dev, generator=g).float()
+    acts2 = torch.randn((m, 2), **f).clamp(-1.0, 1.0)
+    with torch.no_grad():
+        old_lp = pol.log_prob(pol(obs)[0], index) + 0.1 * torch.randn((m,), **f)
+    adv, ret = torch.randn((m,), **f), torch.randn((m,), **f)
+    perm = torch.randperm(m, device=dev, generator=g)
+    mbs = [perm[s:s + bs] for s in range(0, m, bs)]
+    ro = types.SimpleNamespace(n_steps=1, env=types.SimpleNamespace(num_envs=m, state_dim=ns, action_dim=2),
+                               obs=obs.view(1, m, ns), actions=index.view(1, m, 1), log_probs=old_lp.view(1, m),
+                               advantages=adv.view(1, m), returns=ret.view(1, m))
+
+    def adam(p):
+        return torch.optim.Adam(p.parameters(), lr=1e-3, capturable=True)
+
+    def graphed(first, rest):
+        """`first()` eagerly (it packs), then `rest()` captured: the chained minibatches of one pass."""
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            first()
+            rest()  # warm-up of every shape
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            rest()
+        for _ in range(2):
+            graph.replay()
+        torch.cuda.synchronize()
+        return graph
+
+    p_bcd, p_ppo, p_ag, p_g = copy.deepcopy(pol), copy.deepcopy(pol), copy.deepcopy(pol), gauss
+    bcd = BCUpdate(p_bcd, adam(p_bcd), Demonstrations(obs, index), bs)
+    assert bcd._call == "rr_bc_update_discrete"
+    g_bcd = graphed(lambda: bcd(mbs[-1]), lambda: [bcd(idx, chained=True) for idx in mbs])
+    bcg = BCUpdate(p_g, adam(p_g), Demonstrations(obs, acts2), bs)
+    g_bcg = graphed(lambda: bcg(mbs[-1]), lambda: [bcg(idx, chained=True) for idx in mbs])
+    ppo = PPOUpdate(p_ppo, adam(p_ppo), ro, bs)
+    assert ppo._call == "rr_ppo_update_discrete"
+    nxt = mbs[1:] + mbs[:1]  # the last call of a pass prepares the first of the next replay
+    g_ppo = graphed(lambda: ppo(mbs[-1], mbs[0]),
+                    lambda: [ppo(idx, n, chained=True) for idx, n in zip(mbs, nxt)])
+    o_ag = adam(p_ag)
+
+    def autograd_pass():
+        for idx in mbs:
+            loss, _ = _bc_loss(p_ag, obs[idx], index[idx], 1e-3, 0.0)
+            o_ag.zero_grad(set_to_none=True)
+            loss.backward()
+            o_ag.step()
+
+    autograd_pass()
+    torch.cuda.synchronize()
+
+    def timed(fn, passes):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(passes):
+            fn()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) * 1000.0 / (passes * len(mbs))  # us per minibatch
+
+    arms = {"bc_discrete": (g_bcd.replay, args.replays), "bc_gauss": (g_bcg.replay, args.replays),
+            "ppo_discrete": (g_ppo.replay, args.replays), "autograd": (autograd_pass, 1)}
+    samples = {a: [] for a in arms}
+    for _ in range(args.runs):
+        for a, (fn, passes) in arms.items():
+            samples[a].append(timed(fn, passes))
+    med = {a: statistics.median(v) for a, v in samples.items()}
+    finite = all(bool(torch.isfinite(t).all()) for p in (p_bcd, p_g, p_ppo, p_ag) for t in p.parameters())
+    rec = {"rows": m, "batch": bs, "model": "3DOF", "n_choices": k, "minibatches_per_pass": len(mbs), "runs": args.runs,
+           "replays_per_run": args.replays, "device": torch.cuda.get_device_name(0),
+           "library": os.path.basename(_lib.LIB_PATH), "source_hash": build.source_hash(),
+           "unit": "us per minibatch (HIP events; the fused arms: chained calls in a graph replay; autograd: eager)",
+           "parameters_finite_after": finite, "bc_discrete_last_stats": bcd.last_stats(),
+           "bc_discrete_over_ppo_discrete": med["bc_discrete"] / med["ppo_discrete"],
+           "bc_discrete_over_bc_gauss": med["bc_discrete"] / med["bc_gauss"],
+           "autograd_over_bc_discrete": med["autograd"] / med["bc_discrete"]}
+    for a in arms:
+        rec[a] = {"us": samples[a], "median": med[a], "spread": max(samples[a]) - min(samples[a])}
+    print(json.dumps(rec))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(json.dumps(rec, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
