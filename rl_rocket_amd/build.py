@@ -85,10 +85,12 @@ def command(resource_usage=False, out=OUT, defines=(), extra=(), src=SRC, compil
 
 
 def sources():
-    """Every file the translation units are compiled from: all of csrc/, the recording and the
-    exact-mode evaluation's translation units (which include only files of csrc/), the statistics
-    collect's unit with the .inc beside it, the learner-options, behaviour-cloning, discrete-action and
-    discrete behaviour-cloning units and the C-ABI header, sorted (tests/test_build_sources.py checks that the #include graph stays inside this list)."""
+    """Every file the ten translation units are compiled from: all of csrc/ (three units and the
+    text the others include, the behaviour-cloning kernels' rocket_bc.inc among it), the recording and
+    the exact-mode evaluation's units, the statistics collect's unit with the .inc beside it, the
+    learner-options, behaviour-cloning, discrete-action and discrete behaviour-cloning units and the
+    C-ABI header, sorted (tests/test_build_sources.py checks that the #include graph stays inside this
+    list)."""
     csrc = os.path.join(HERE, "csrc")
     return sorted([os.path.join(csrc, f) for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))]
                   + [SRC_EVAL_TRACE, SRC_EVAL_EXACT, SRC_COLLECT_STATS, INC_COLLECT_STATS, SRC_PPO_OPTS, SRC_BC, SRC_DISCRETE,
@@ -111,8 +113,8 @@ def source_hash():
 
 
 def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
-    """The six steps of the library build: the main, exact-mode, collect, recording-evaluation and
-    exact-evaluation translation units compiled to objects (the latter four with EXACT_FLAGS /
+    """The six hipcc calls that build the library's ten translation units: the main, exact-mode,
+    collect, recording-evaluation and exact-evaluation units compiled to objects (the latter four with EXACT_FLAGS /
     COLLECT_FLAGS / COLLECT_FLAGS / EVAL_EXACT_FLAGS); the last step compiles the learner-options, the
     behaviour-cloning, the discrete-action, the discrete behaviour-cloning and the statistics collect's units
     (all COLLECT_FLAGS, each a module of its own) and links them with
@@ -137,7 +139,8 @@ def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
 
 
 def build_lib(out=OUT, defines=(), extra=(), resource_usage=False, verbose=True, preload=4):
-    """Compile five translation units to objects (in parallel), then the sixth with the link of `out`."""
+    """Compile five translation units to objects (in parallel), then the other five in the call that
+    links `out`."""
     cmds = commands(resource_usage, out, defines, extra, preload=preload)
     if verbose:
         for c in cmds:

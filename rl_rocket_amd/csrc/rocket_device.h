@@ -1219,6 +1219,6 @@ __attribute__((visibility("hidden"))) int rrc_launch_learner_opts(const void* la
 __attribute__((visibility("hidden"))) int rrc_launch_bc(const void* launch, void* stream);
 // discrete/rocket_discrete.hip: the Categorical policy's launches, a DiscreteLaunch
 __attribute__((visibility("hidden"))) int rrc_launch_discrete(const void* launch, void* stream);
-// bc_discrete/rocket_bc_discrete.hip: rr_bc_update_discrete's launches, a BcDiscreteLaunch
+// bc_discrete/rocket_bc_discrete.hip: rr_bc_update_discrete's launches, a BcLaunch with n_choices and a sink
 __attribute__((visibility("hidden"))) int rrc_launch_bc_discrete(const void* launch, void* stream);
 }

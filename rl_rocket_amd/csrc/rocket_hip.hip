@@ -1707,15 +1707,16 @@ void ppo_carve(PpoLaunch& L, const LearnerShape& sh, int64_t batch, void* worksp
 // The finish kernel's squared-gradient sums (two towers) and the step count, in floats, 16-B rows
 int64_t norm_floats(const LearnerShape& sh) { return (2 * sh.fin() + 1 + 3) / 4 * 4; }
 
-// rr_bc_update's workspace: 2 packed tower images | the finish's per-block sums and the step count,
-// 16-B rows | nwg partial-gradient vectors. What a call leaves for the chained one (the images) sits
-// ahead of the only section whose size follows the batch, as in ppo_carve.
+// rr_bc_update's and rr_bc_update_discrete's workspace: 2 packed tower images | the finish's per-block
+// sums and the step count, 16-B rows | the Categorical policy's sink (sink_floats; 0 for the Gaussian) |
+// nwg partial-gradient vectors. What a call leaves for the chained one (the images) sits ahead of the
+// only section whose size follows the batch, as in ppo_carve.
 int64_t bc_fixed_floats(const LearnerShape& sh) { return 2 * sh.pack + norm_floats(sh); }
 
-// rr_bc_update_workspace_size's bytes for a shape that passed
-int64_t bc_bytes(const LearnerShape& sh, int64_t batch)
+// the two rr_bc_update*_workspace_size calls' bytes for a shape that passed
+int64_t bc_bytes(const LearnerShape& sh, int64_t batch, int64_t sink_floats)
 {
-    int64_t floats = bc_fixed_floats(sh) + ppo_nwg(batch) * sh.part;
+    int64_t floats = bc_fixed_floats(sh) + sink_floats + ppo_nwg(batch) * sh.part;
 #if defined(RR_DIAG_STAMPS)
     // the shared gradient body writes its stamps past two towers' partial vectors: 16 floats per wave
     floats += ppo_nwg(batch) * (sh.part + ppo::kWaves * 16);
@@ -1723,12 +1724,18 @@ int64_t bc_bytes(const LearnerShape& sh, int64_t batch)
     return floats * (int64_t)sizeof(float);
 }
 
-// The shape checks of the four *_workspace_size calls (sized: `bytes` is required too) and of rr_bc_update
+// The minibatch check of every learner entry point (sized: a *_workspace_size call, `bytes` is required too)
+static int learner_batch_ok(const char* who, int64_t batch, const int64_t* bytes, bool sized = true)
+{
+    if (batch < 2 || (sized && !bytes)) return refuse(who, sized ? "batch >= 2 and bytes required" : "batch >= 2 required");
+    return RR_OK;
+}
+
+// The shape checks of the Gaussian policy's four *_workspace_size calls and of rr_bc_update
 int learner_shape_ok(const char* who, const LearnerShape& sh, int64_t batch, const int64_t* bytes, bool sized = true)
 {
     if (!sh.part) return refuse(who, "supported (obs_dim, act_dim) are (14, 3) and (7, 2)");
-    if (batch < 2 || (sized && !bytes)) return refuse(who, sized ? "batch >= 2 and bytes required" : "batch >= 2 required");
-    return RR_OK;
+    return learner_batch_ok(who, batch, bytes, sized);
 }
 
 // rr_ppo_workspace_size's bytes for a shape that passed: ppo_carve's three sections
@@ -1997,38 +2004,32 @@ int rr_ppo_update_opts(int obs_dim, int act_dim, float* const* params, float* co
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_opts: launch");
 }
 
-int rr_bc_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
+namespace {
+// The argument checks and launch record of rr_bc_update and rr_bc_update_discrete, for a shape and batch that
+// passed (`who` names the entry point in the error text; sink_floats is the Categorical policy's sink and
+// log_std slot, 0 for the Gaussian)
+static int bc_update_record(const char* who, BcLaunch& L, const LearnerShape& sh, int64_t sink_floats, float* const* params,
+                     float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, float* const* step,
+                     const float* obs, const float* actions, const int64_t* idx, int64_t batch, float ent_weight,
+                     float l2_weight, const float* lr, double beta1, double beta2, float eps, float* stats,
+                     uint32_t flags, void* workspace, int64_t workspace_bytes)
 {
-    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
-    if (const int rc = learner_shape_ok("rr_bc_update_workspace_size", sh, batch, bytes); rc != RR_OK) return rc;
-    *bytes = bc_bytes(sh, batch);
-    return RR_OK;
-}
-
-int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* exp_avg,
-                 float* const* exp_avg_sq, float* const* step, const float* obs, const float* actions,
-                 const int64_t* idx, int64_t batch, float ent_weight, float l2_weight, const float* lr,
-                 double beta1, double beta2, float eps, float* stats, uint32_t flags,
-                 void* workspace, int64_t workspace_bytes, void* stream)
-{
-    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
-    if (const int rc = learner_shape_ok("rr_bc_update", sh, batch, nullptr, false); rc != RR_OK) return rc;
-    const int64_t need = bc_bytes(sh, batch);
     if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !obs || !actions || !idx || !lr)
-        return fail(RR_EINVAL, "rr_bc_update: null argument");
-    const int rc = learner_ws_ok("rr_bc_update", workspace, workspace_bytes, need, flags, RR_BC_CHAINED);
+        return refuse(who, "null argument");
+    const int rc = learner_ws_ok(who, workspace, workspace_bytes, bc_bytes(sh, batch, sink_floats), flags, RR_BC_CHAINED);
     if (rc != RR_OK) return rc;
     // NaN fails the comparison too
-    if (!(ent_weight >= 0.0f)) return fail(RR_EINVAL, "rr_bc_update: ent_weight must be >= 0");
-    if (!(l2_weight >= 0.0f)) return fail(RR_EINVAL, "rr_bc_update: l2_weight must be >= 0");
-    BcLaunch L = {};
+    if (!(ent_weight >= 0.0f)) return refuse(who, "ent_weight must be >= 0");
+    if (!(l2_weight >= 0.0f)) return refuse(who, "l2_weight must be >= 0");
+    L = {};
     if (!bind_policy(L.ps, L.pg, &L.a, sh, params, grads, exp_avg, exp_avg_sq, step))
-        return fail(RR_EINVAL, "rr_bc_update: null parameter, gradient or optimizer-state tensor");
-    L.obs_dim = obs_dim;
+        return refuse(who, "null parameter, gradient or optimizer-state tensor");
+    L.obs_dim = sh.obs_dim;
     L.nwg = (int)ppo_nwg(batch);
     L.pack = (float*)workspace;
     L.normw = L.pack + 2 * sh.pack;
-    L.part = L.pack + bc_fixed_floats(sh);
+    L.sink = sink_floats ? L.pack + bc_fixed_floats(sh) : nullptr;
+    L.part = L.pack + bc_fixed_floats(sh) + sink_floats;
     L.nbp = (int)((L.a.wstart[sh.n] + kAdamThreads - 1) / kAdamThreads);
     L.obs = obs;
     L.actions = actions;
@@ -2039,6 +2040,31 @@ int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* g
     set_adam(L, lr, beta1, beta2, eps);
     L.stats = stats;
     L.flags = flags;
+    return RR_OK;
+}
+}  // namespace
+
+int rr_bc_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
+{
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
+    const int rc = learner_shape_ok("rr_bc_update_workspace_size", sh, batch, bytes);
+    if (rc == RR_OK) *bytes = bc_bytes(sh, batch, 0);
+    return rc;
+}
+
+int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* exp_avg,
+                 float* const* exp_avg_sq, float* const* step, const float* obs, const float* actions,
+                 const int64_t* idx, int64_t batch, float ent_weight, float l2_weight, const float* lr,
+                 double beta1, double beta2, float eps, float* stats, uint32_t flags,
+                 void* workspace, int64_t workspace_bytes, void* stream)
+{
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
+    if (const int rc = learner_shape_ok("rr_bc_update", sh, batch, nullptr, false); rc != RR_OK) return rc;
+    BcLaunch L;
+    const int rc = bc_update_record("rr_bc_update", L, sh, 0, params, grads, exp_avg, exp_avg_sq, step, obs, actions, idx,
+                                    batch, ent_weight, l2_weight, lr, beta1, beta2, eps, stats, flags, workspace,
+                                    workspace_bytes);
+    if (rc != RR_OK) return rc;
     const hipError_t err = (hipError_t)rrc_launch_bc(&L, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_bc_update: launch");
 }
@@ -2052,6 +2078,13 @@ int disc_shape_ok(const char* who, int obs_dim, int n_choices)
     if (obs_dim != 7) return refuse(who, "obs_dim must be 7 (the 3DOF env)");
     if (n_choices < 2 || n_choices > 4) return refuse(who, "n_choices must be in 2 .. 4");
     return RR_OK;
+}
+
+// learner_shape_ok for the Categorical policy's learner calls
+static int disc_learner_ok(const char* who, int obs_dim, int n_choices, int64_t batch, const int64_t* bytes, bool sized = true)
+{
+    if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
+    return learner_batch_ok(who, batch, bytes, sized);
 }
 
 // The <7, 4> image with n_choices action-head rows over the 12 tensors of a policy without a log_std
@@ -2127,12 +2160,10 @@ int rr_policy_act_discrete(const float* params, int obs_dim, int n_choices, cons
 
 int rr_ppo_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes)
 {
-    const char* who = "rr_ppo_update_discrete_workspace_size";
-    if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
-    if (batch < 2 || !bytes) return refuse(who, "batch >= 2 and bytes required");
+    const int rc = disc_learner_ok("rr_ppo_update_discrete_workspace_size", obs_dim, n_choices, batch, bytes);
     // rr_ppo_update's sections (ppo_carve, the finish's sums), then the sink
-    *bytes = ppo_update_bytes(disc_shape(n_choices), batch) + kDiscSink * (int64_t)sizeof(float);
-    return RR_OK;
+    if (rc == RR_OK) *bytes = ppo_update_bytes(disc_shape(n_choices), batch) + kDiscSink * (int64_t)sizeof(float);
+    return rc;
 }
 
 int rr_ppo_update_discrete(int obs_dim, int n_choices, float* const* params, float* const* grads,
@@ -2144,8 +2175,7 @@ int rr_ppo_update_discrete(int obs_dim, int n_choices, float* const* params, flo
                            void* workspace, int64_t workspace_bytes, void* stream)
 {
     const char* who = "rr_ppo_update_discrete";
-    if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
-    if (batch < 2) return refuse(who, "batch >= 2 required");
+    if (const int rc = disc_learner_ok(who, obs_dim, n_choices, batch, nullptr, false); rc != RR_OK) return rc;
     const LearnerShape sh = disc_shape(n_choices);
     const int64_t sink_at = ppo_update_bytes(sh, batch);
     DiscreteLaunch D = {};
@@ -2162,25 +2192,11 @@ int rr_ppo_update_discrete(int obs_dim, int n_choices, float* const* params, flo
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_discrete: launch");
 }
 
-namespace {
-// rr_bc_update_discrete's workspace: rr_bc_update's fixed sections over the <7, 4> image (2 packed tower
-// images | the finish's sums and the step count), the sink, then the nwg partial-gradient vectors: again
-// the only section whose size follows the batch is the last
-int64_t bc_disc_fixed_floats(const LearnerShape& sh) { return bc_fixed_floats(sh) + kDiscSink; }
-
-int64_t bc_disc_bytes(const LearnerShape& sh, int64_t batch)
-{
-    return bc_bytes(sh, batch) + kDiscSink * (int64_t)sizeof(float);
-}
-}  // namespace
-
 int rr_bc_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes)
 {
-    const char* who = "rr_bc_update_discrete_workspace_size";
-    if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
-    if (batch < 2 || !bytes) return refuse(who, "batch >= 2 and bytes required");
-    *bytes = bc_disc_bytes(disc_shape(n_choices), batch);
-    return RR_OK;
+    const int rc = disc_learner_ok("rr_bc_update_discrete_workspace_size", obs_dim, n_choices, batch, bytes);
+    if (rc == RR_OK) *bytes = bc_bytes(disc_shape(n_choices), batch, kDiscSink);
+    return rc;
 }
 
 int rr_bc_update_discrete(int obs_dim, int n_choices, float* const* params, float* const* grads,
@@ -2190,39 +2206,15 @@ int rr_bc_update_discrete(int obs_dim, int n_choices, float* const* params, floa
                           void* workspace, int64_t workspace_bytes, void* stream)
 {
     const char* who = "rr_bc_update_discrete";
-    if (const int rc = disc_shape_ok(who, obs_dim, n_choices); rc != RR_OK) return rc;
-    if (batch < 2) return refuse(who, "batch >= 2 required");
-    const LearnerShape sh = disc_shape(n_choices);
-    if (!params || !grads || !exp_avg || !exp_avg_sq || !step || !obs || !actions || !idx || !lr)
-        return refuse(who, "null argument");
-    const int rc = learner_ws_ok(who, workspace, workspace_bytes, bc_disc_bytes(sh, batch), flags, RR_BC_CHAINED);
+    if (const int rc = disc_learner_ok(who, obs_dim, n_choices, batch, nullptr, false); rc != RR_OK) return rc;
+    BcLaunch L;
+    const int rc = bc_update_record(who, L, disc_shape(n_choices), kDiscSink, params, grads, exp_avg, exp_avg_sq, step,
+                                    obs, actions, idx, batch, ent_weight, l2_weight, lr, beta1, beta2, eps, stats, flags,
+                                    workspace, workspace_bytes);
     if (rc != RR_OK) return rc;
-    // NaN fails the comparison too
-    if (!(ent_weight >= 0.0f)) return refuse(who, "ent_weight must be >= 0");
-    if (!(l2_weight >= 0.0f)) return refuse(who, "l2_weight must be >= 0");
-    BcDiscreteLaunch D = {};
-    BcLaunch& L = D.b;
-    if (!bind_policy(L.ps, L.pg, &L.a, sh, params, grads, exp_avg, exp_avg_sq, step))
-        return refuse(who, "null parameter, gradient or optimizer-state tensor");
-    D.n_choices = n_choices;
-    L.obs_dim = obs_dim;
-    L.nwg = (int)ppo_nwg(batch);
-    L.pack = (float*)workspace;
-    L.normw = L.pack + 2 * sh.pack;
-    D.sink = L.pack + bc_fixed_floats(sh);
-    L.pg.p[12] = D.sink + 64 * 4 + 4;  // log_std's slot of the finish body
-    L.part = L.pack + bc_disc_fixed_floats(sh);
-    L.nbp = (int)((L.a.wstart[sh.n] + kAdamThreads - 1) / kAdamThreads);
-    L.obs = obs;
-    L.actions = actions;
-    L.idx = idx;
-    L.batch = batch;
-    L.ent = ent_weight;
-    L.l2 = l2_weight;
-    set_adam(L, lr, beta1, beta2, eps);
-    L.stats = stats;
-    L.flags = flags;
-    const hipError_t err = (hipError_t)rrc_launch_bc_discrete(&D, stream);
+    L.n_choices = n_choices;
+    L.pg.p[12] = L.sink + 64 * 4 + 4;  // log_std's slot of the finish body
+    const hipError_t err = (hipError_t)rrc_launch_bc_discrete(&L, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_bc_update_discrete: launch");
 }
 

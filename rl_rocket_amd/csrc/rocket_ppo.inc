@@ -881,8 +881,11 @@ struct PpoOptsLaunch {
 };
 static_assert(std::is_trivially_copyable_v<PpoOptsLaunch>, "PpoOptsLaunch crosses TUs by memcpy");
 
-// rr_bc_update's launches (bc/rocket_bc.hip, rrc_launch_bc): pack the pi image, the pi tower's
-// gradient on nwg workgroups, the finish over both halves and the statistics, Adam with the repack
+// rr_bc_update's and rr_bc_update_discrete's launches (rocket_bc.inc; rrc_launch_bc, rrc_launch_bc_discrete):
+// pack the pi image, the pi tower's gradient on nwg workgroups, the finish over both halves and the
+// statistics, Adam with the repack. For the Categorical policy the record is over 12 tensors, pg.p[12] is
+// four spare floats of the workspace and `sink` 260 more (where the finish puts the zero sums of heads >=
+// n_choices); for the Gaussian n_choices is 0 and sink null.
 struct BcLaunch {
     PolSrc ps;
     PolGrad pg;
@@ -895,6 +898,8 @@ struct BcLaunch {
     float *part, *pack, *normw;
     int obs_dim, nwg, nbp;
     uint32_t flags;
+    int n_choices;
+    float* sink;
 };
 static_assert(std::is_trivially_copyable_v<BcLaunch>, "BcLaunch crosses TUs by memcpy");
 
@@ -921,16 +926,6 @@ struct DiscreteLaunch {
     float gamma;
 };
 static_assert(std::is_trivially_copyable_v<DiscreteLaunch>, "DiscreteLaunch crosses TUs by memcpy");
-
-// rr_bc_update_discrete's launches (bc_discrete/rocket_bc_discrete.hip, rrc_launch_bc_discrete): an
-// rr_bc_update record over 12 tensors whose pg.p[12] is four spare floats of the workspace, the number of
-// choices, and `sink`, 260 floats (where the finish puts the zero sums of heads >= n_choices)
-struct BcDiscreteLaunch {
-    BcLaunch b;
-    int n_choices;
-    float* sink;
-};
-static_assert(std::is_trivially_copyable_v<BcDiscreteLaunch>, "BcDiscreteLaunch crosses TUs by memcpy");
 
 // Element k of policy tensor t (rr_ppo_grad order) into the packed images (two towers of Pack::SIZE).
 template <int OBS, int ACT>

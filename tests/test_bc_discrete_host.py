@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import bc_discrete_ref as R
+import bc_host_common as C
 import discrete_ref as D
 from rl_rocket_amd import _lib
 from rl_rocket_amd import build as B
@@ -157,62 +158,11 @@ def test_python_refusals():
     assert r.acts.shape == (32, 1) and r.acts.data_ptr() == ro.actions.data_ptr()
 
 
-def _ptrs(k, null_at=None):
-    arr = (ctypes.c_void_p * k)(*[0x10000 + 0x1000 * i for i in range(k)])
-    if null_at is not None:
-        arr[null_at] = None
-    return arr
-
-
 def test_c_abi_refuses_bad_arguments_before_any_hip_call():
-    """Never-read fake device addresses and a NULL stream: every refusal returns RR_EINVAL with a message
-    that names the entry point, before a launch."""
-    lib = _lib.load()
-    E, V = _lib.RR_EINVAL, ctypes.c_void_p
-    fake, lr = V(0x10000), V(0x20000)
-    nbytes = ctypes.c_int64()
-    sz = "rr_bc_update_discrete_workspace_size"
-
-    def refused(rc, name, word=None):
-        assert rc == E, (name, rc)
-        msg = lib.rr_last_error()
-        assert msg.startswith(name.encode() + b": ") and (word is None or word.encode() in msg), (name, msg)
-
-    refused(lib.rr_bc_update_discrete_workspace_size(14, 4, 64, ctypes.byref(nbytes)), sz, "obs_dim")
-    refused(lib.rr_bc_update_discrete_workspace_size(7, 5, 64, ctypes.byref(nbytes)), sz, "n_choices")
-    refused(lib.rr_bc_update_discrete_workspace_size(7, 1, 64, ctypes.byref(nbytes)), sz, "n_choices")
-    refused(lib.rr_bc_update_discrete_workspace_size(7, 4, 1, ctypes.byref(nbytes)), sz, "batch")
-    refused(lib.rr_bc_update_discrete_workspace_size(7, 4, 64, None), sz)
-    assert lib.rr_bc_update_discrete_workspace_size(7, 4, 4096, ctypes.byref(nbytes)) == _lib.RR_OK
-    need = nbytes.value
-    nan = float("nan")
-
-    def call(shape=(7, 4), lists=None, obs=fake, acts=fake, idx=fake, batch=4096, ent=1e-3, l2=0.0, lr_p=lr, stats=None,
-             flags=0, ws=V(0x200000), ws_bytes=need):
-        lists = lists or [_ptrs(12)] * 5
-        return lib.rr_bc_update_discrete(*shape, *lists, obs, acts, idx, batch, ent, l2, lr_p, 0.9, 0.999, 1e-8, stats,
-                                         flags, ws, ws_bytes, None)
-
-    who = "rr_bc_update_discrete"
-    refused(call(shape=(7, 1)), who, "n_choices")
-    refused(call(shape=(7, 5)), who, "n_choices")
-    refused(call(shape=(14, 4)), who, "obs_dim")
-    refused(call(shape=(14, 3)), who, "obs_dim")
-    refused(call(batch=1), who, "batch")
-    refused(call(batch=-5), who, "batch")
-    for k in range(5):
-        refused(call(lists=[_ptrs(12) if j != k else None for j in range(5)]), who, "null")
-        refused(call(lists=[_ptrs(12) if j != k else _ptrs(12, null_at=8 + k % 4) for j in range(5)]), who, "tensor")
-    for name in ("obs", "acts", "idx", "lr_p", "ws"):
-        refused(call(**{name: None}), who, "null")
-    refused(call(ws_bytes=need - 16), who, "workspace")
-    refused(call(batch=8192), who, "workspace")  # a workspace sized for 4096 rows: 32 workgroups, not 64
-    refused(call(ws=V(0x200008)), who, "16-B")
-    for bad in (nan, -0.1, -float("inf")):
-        refused(call(ent=bad), who, "ent_weight")
-        refused(call(l2=bad), who, "l2_weight")
-    for flags in (0x2, 0x4, 0x80000001):
-        refused(call(flags=flags), who, "flag")
+    """Never-read fake device addresses and a NULL stream: every refusal returns RR_EINVAL with the message
+    it had before the two calls shared their host path, before a launch."""
+    C.check_refusals("rr_bc_update_discrete", (7, 4), 12, [((14, 4), C.CAT_OBS), ((14, 3), C.CAT_OBS), ((5, 2), C.CAT_OBS),
+                                                            ((7, 5), C.CAT_K), ((7, 1), C.CAT_K)])
 
 
 def test_workspace_size_grows_with_batch_and_is_one_tower():
@@ -230,6 +180,7 @@ def test_workspace_size_grows_with_batch_and_is_one_tower():
         # one tower's partial vectors: less than the PPO call's two
         assert lib.rr_ppo_update_discrete_workspace_size(7, k, 65536, ctypes.byref(b)) == _lib.RR_OK
         assert sizes[5] < b.value
+    C.check_workspace_sizes("rr_bc_update_discrete")
 
 
 def test_header_signatures_and_exports():
@@ -253,34 +204,13 @@ def test_header_signatures_and_exports():
 
 
 def test_build_compiles_the_translation_unit_of_its_own():
-    src = B.SRC_BC_DISCRETE
-    csrc = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc")
-    assert os.path.dirname(src) == os.path.join(csrc, "bc_discrete") and os.path.isfile(src)
-    assert src in B.sources() and B.sources() == sorted(B.sources())
-    cmds = B.commands()
-    mine = [c for c in cmds if src in c]
-    assert mine == [cmds[-1]] and "-shared" in mine[0]  # compiled in the linking step, a module of its own
-    assert mine[0].index(B.SRC_DISCRETE) < mine[0].index(src) < mine[0].index(B.SRC_COLLECT_STATS)
-    for flag in B.COLLECT_FLAGS:  # the learner's code-generation setting
-        assert flag in mine[0]
-    assert not any(f in mine[0] for f in B.EXACT_FLAGS if f != "-mllvm")
-    assert os.listdir(os.path.dirname(src)) == ["rocket_bc_discrete.hip"]
-    text = open(src).read()
-    assert text.index("#define RR_POL_PREFETCH_A 1") < text.index('#include "rocket_policy.inc"')
-    incs = re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', text, flags=re.M)
-    # the learner's bodies, not copies of them
-    assert {"rocket_ppo.inc", "rocket_ppo_finish_body.inc", "rocket_ppo_adam_body.inc"} <= set(incs)
-    assert "ppo_grad_tower<OBS, ACT, 0, false, false, 3>" in text and "__builtin_amdgcn_mfma" not in text
-    for inc in incs:
-        assert os.path.join(csrc, inc) in B.sources() and not inc.endswith(".hip"), inc
+    C.check_unit(B.SRC_BC_DISCRETE, "bc_discrete", B.SRC_DISCRETE, 1)
 
 
 def test_new_kernels_use_no_scratch():
     """From the built library: the four new kernels, one instantiation each, with no scratch
     (private_segment_fixed_size, bytes 4..8 of the kernel descriptor)."""
-    import test_bc_host
-
-    kd = test_bc_host._kernel_descriptors()
+    kd = C.kernel_descriptors()
     new = {n: v for n, v in kd.items() if "bcd_" in n and "_kernel" in n}
     for name in ("bcd_pack_kernel", "bcd_grad_kernel", "bcd_finish_kernel", "bcd_adam_kernel"):
         assert sum(name + "ILi7ELi4E" in n for n in new) == 1, name

@@ -11,13 +11,13 @@ import re
 import struct
 import subprocess
 import sys
-import tempfile
 import types
 
 import numpy as np
 import pytest
 import torch
 
+import bc_host_common as C
 import bc_ref as R
 import ppo_ref as P
 from rl_rocket_amd import _lib
@@ -89,97 +89,31 @@ def test_library_exports_the_symbols_and_keeps_the_launcher_hidden():
 
 
 def test_refuses_bad_arguments_before_any_hip_call():
-    """Never-read fake device addresses and a NULL stream: every refusal returns before a launch."""
+    """Never-read fake device addresses and a NULL stream: every refusal returns before a launch, with the
+    text it had before the two calls shared their host path."""
+    C.check_refusals("rr_bc_update", (14, 3), 13, [((5, 2), C.GAUSS_SHAPE), ((14, 2), C.GAUSS_SHAPE),
+                                                     ((7, 3), C.GAUSS_SHAPE), ((7, 4), C.GAUSS_SHAPE)])
+    # rr_ppo_update keeps its own prefix
     lib = _lib.load()
     V = ctypes.c_void_p
-    fake = (V * 13)(*[0x100000 + 0x1000 * k for k in range(13)])
-    p = V(0x70000)
-    nbytes = ctypes.c_int64()
-    assert lib.rr_bc_update_workspace_size(14, 3, 4096, ctypes.byref(nbytes)) == _lib.RR_OK
-    nan = float("nan")
-
-    def call(obs_dim=14, act_dim=3, params=fake, grads=fake, m=fake, v=fake, step=fake, obs=p, acts=p, idx=p, batch=4096,
-             ent=1e-3, l2=0.0, lr=p, stats=p, flags=0, ws=V(0x200000), ws_bytes=None):
-        return lib.rr_bc_update(obs_dim, act_dim, params, grads, m, v, step, obs, acts, idx, batch, ent, l2, lr, 0.9,
-                                0.999, 1e-8, stats, flags, ws, nbytes.value if ws_bytes is None else ws_bytes, None)
-
-    def refused(rc, word):
-        assert rc == _lib.RR_EINVAL
-        msg = lib.rr_last_error()
-        assert msg.startswith(b"rr_bc_update: ") and word in msg, msg
-
-    for bad in (nan, -0.1, -float("inf")):
-        refused(call(ent=bad), b"ent_weight")
-        refused(call(l2=bad), b"l2_weight")
-    for flags in (0x2, 0x4, 0x80000001):
-        refused(call(flags=flags), b"flag")
-    # what rr_ppo_update refuses that applies here
-    refused(call(obs_dim=5), b"obs_dim")
-    refused(call(act_dim=2), b"obs_dim")
-    refused(call(obs_dim=7, act_dim=3), b"obs_dim")
-    refused(call(batch=1), b"batch")
-    refused(call(batch=-5), b"batch")
-    for name in ("params", "grads", "m", "v", "step", "obs", "acts", "idx", "lr", "ws"):
-        refused(call(**{name: None}), b"null")
-    holes = (V * 13)(*[0x100000 + 0x1000 * k if k != 7 else 0 for k in range(13)])
-    for name in ("params", "grads", "m", "v", "step"):
-        refused(call(**{name: holes}), b"null")
-    refused(call(ws=V(0x200008)), b"16-B")
-    refused(call(ws_bytes=nbytes.value - 16), b"workspace")
-    refused(call(batch=8192), b"workspace")  # a workspace sized for 4096 rows: 32 workgroups, not 64
-    # rr_ppo_update keeps its own prefix
+    fake, p = (V * 13)(*[0x100000 + 0x1000 * k for k in range(13)]), V(0x70000)
     assert lib.rr_ppo_update(14, 3, fake, fake, fake, fake, fake, p, p, p, p, p, p, 4096, None, 0, 0.2, 0.01, 0.5, 0.5, p,
                              0.9, 0.999, 1e-5, p, 0x2, V(0x200000), 1 << 30, None) == _lib.RR_EINVAL
     assert lib.rr_last_error() == b"rr_ppo_update: unknown flag bits"
 
 
+def test_workspace_sizes_are_the_ones_before_the_fold():
+    C.check_workspace_sizes("rr_bc_update")
+
+
 def test_build_compiles_the_translation_unit_of_its_own():
-    src = B.SRC_BC
-    csrc = os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc")
-    assert os.path.dirname(src) == os.path.join(csrc, "bc") and os.path.isfile(src)
-    assert src in B.sources() and B.sources() == sorted(B.sources())
-    cmds = B.commands()
-    assert len(cmds) == 6  # five compile steps and the link
-    mine = [c for c in cmds if src in c]
-    assert mine == [cmds[-1]] and "-shared" in mine[0]  # compiled in the linking step, a module of its own
-    assert mine[0].index(B.SRC_PPO_OPTS) < mine[0].index(src) < mine[0].index(B.SRC_COLLECT_STATS)
-    assert mine[0][-1] == B.SRC_COLLECT_STATS
-    for flag in B.COLLECT_FLAGS:  # the learner's code-generation setting
-        assert flag in mine[0]
-    assert not any(f in mine[0] for f in B.EXACT_FLAGS if f != "-mllvm")
-    assert os.listdir(os.path.dirname(src)) == ["rocket_bc.hip"]
-    text = open(src).read()
-    assert text.index("#define RR_POL_PREFETCH_A 1") < text.index('#include "rocket_policy.inc"')
-    incs = re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', text, flags=re.M)
-    # the learner's bodies, not copies of them
-    assert {"rocket_ppo.inc", "rocket_ppo_finish_body.inc", "rocket_ppo_adam_body.inc"} <= set(incs)
-    assert "ppo_grad_tower<OBS, ACT, 0, false, false, 1>" in text and "__builtin_amdgcn_mfma" not in text
-    for inc in incs:
-        assert os.path.join(csrc, inc) in B.sources() and not inc.endswith(".hip"), inc
-
-
-def _kernel_descriptors():
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    kd = {}
-    with tempfile.TemporaryDirectory() as d:
-        fat = os.path.join(d, "fat.bin")
-        subprocess.check_call([B._llvm("llvm-objcopy"), "--dump-section=.hip_fatbin=" + fat, B.OUT, os.path.join(d, "x")])
-        blob = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(magic), blob)]
-        for k, k0 in enumerate(starts):
-            part, co = os.path.join(d, "b%d.bin" % k), os.path.join(d, "b%d.co" % k)
-            with open(part, "wb") as f:
-                f.write(blob[k0:starts[k + 1] if k + 1 < len(starts) else len(blob)])
-            subprocess.check_call([B._llvm("clang-offload-bundler"), "--unbundle", "--type=o", "--input=" + part,
-                                   "--targets=hipv4-amdgcn-amd-amdhsa--%s" % B.ARCH, "--output=" + co])
-            kd.update({n: v for n, v in B._elf_symbols(open(co, "rb").read()).items() if n.endswith(".kd")})
-    return kd
+    C.check_unit(B.SRC_BC, "bc", B.SRC_PPO_OPTS, 0)
 
 
 def test_new_kernels_use_no_scratch_and_the_learner_kernels_are_all_there():
     """From the built library: the new instantiations use no scratch (private_segment_fixed_size,
     bytes 4..8 of the kernel descriptor) and the learner's own kernels are still beside them."""
-    kd = _kernel_descriptors()
+    kd = C.kernel_descriptors()
     new = {n: v for n, v in kd.items() if "bc_" in n and "_kernel" in n}
     for name in ("bc_pack_kernel", "bc_grad_kernel", "bc_finish_kernel", "bc_adam_kernel"):  # two shapes of each
         assert sum(name + "IL" in n for n in new) == 2, name
@@ -197,6 +131,20 @@ def test_committed_isa_comparison_covers_every_kernel_of_the_parent():
     assert all(rec["after"][k] == h for k, h in rec["before"].items())
     assert sorted(rec["added"]) == sorted(k for k in rec["after"] if k not in rec["before"])
     assert len(rec["added"]) == 8 and all("::bc_" in k for k in rec["added"])
+
+
+def test_committed_isa_comparison_of_the_fold_covers_every_kernel_of_the_parent():
+    """profiles/bc_fold: the two units on one kernel text against the build before it, no kernel renamed. The
+    parent's kernels are the ones its own record (profiles/bc_discrete, `after`) lists: all 179, each with
+    the hash it had there."""
+    with open(os.path.join(ROOT, "profiles", "bc_fold", "isa_before_after.json")) as f:
+        rec = json.load(f)
+    with open(os.path.join(ROOT, "profiles", "bc_discrete", "isa_before_after.json")) as f:
+        parent = json.load(f)["after"]
+    assert rec["kernels_A"] == rec["kernels_B"] == len(rec["hashes"]) == len(parent) == 179
+    assert rec["only in A"] == rec["only in B"] == rec["hash differs"] == [] and rec["renamed"] == {}
+    assert rec["hashes"] == parent
+    assert sum("::bc_" in k for k in parent) == 8 and sum("::bcd_" in k for k in parent) == 4
 
 
 def test_bc_ref_against_a_closed_form():

@@ -1,5 +1,5 @@
 """The library's source list (no GPU, no compile): the #include graph of the three translation
-units stays inside rl_rocket_amd.build.sources() (what source_hash() and up_to_date() read), no file
+units of csrc/ and of the two behaviour-cloning units stays inside rl_rocket_amd.build.sources() (what source_hash() and up_to_date() read), no file
 of csrc/ is an orphan, no .hip file includes another, and tools/ab_exact_cap.py's anchors still
 match the exact solver's text."""
 import importlib.util
@@ -32,7 +32,8 @@ def includes(path):
 
 @pytest.fixture(scope="module")
 def reached():
-    seen, todo = set(), [B.SRC, B.SRC_EXACT, B.SRC_COLLECT]
+    # the three units of csrc/ and the two behaviour-cloning units, whose shared kernel text lies in csrc/
+    seen, todo = set(), [B.SRC, B.SRC_EXACT, B.SRC_COLLECT, B.SRC_BC, B.SRC_BC_DISCRETE]
     while todo:
         p = os.path.normpath(todo.pop())
         if p not in seen:

@@ -25,67 +25,16 @@ import pytest
 
 import bc_ref as R
 import ppo_ref as P
+from bc_gpu_common import BcHelpers
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 N_ROWS = R.N_ROWS
 
-
-def _minibatch(bs, extra=0):
-    import torch
-
-    g = torch.Generator().manual_seed(bs)
-    return torch.randperm(N_ROWS, generator=g)[:bs + extra].contiguous().cuda()
-
-
-def _adam(pol, lr=1e-3, **kw):
-    import torch
-
-    return torch.optim.Adam(pol.parameters(), lr=lr, capturable=True, **kw)
-
-
-def _one_call(pol0, obs, acts, idx, ent_weight=1e-3, l2_weight=0.0):
-    """A copy of pol0 after one rr_bc_update on idx: (policy, its gradients fp32, the 8 stats)."""
-    import torch
-    from rl_rocket_amd.bc import BCUpdate, Demonstrations
-    from rl_rocket_amd.rollout import _policy_tensors
-
-    pol = copy.deepcopy(pol0)
-    step = BCUpdate(pol, _adam(pol), Demonstrations(obs, acts), idx.numel(), ent_weight, l2_weight)
-    stats = step(idx).clone()
-    torch.cuda.synchronize()
-    return pol, [t.grad.clone() for t in _policy_tensors(pol)], stats
-
-
-def _check_against_fp64(label, pol0, obs, acts, idx, grads, stats, ent_weight=1e-3, l2_weight=0.0):
-    """The learner's bars on the gradients a call left and its statistics; pol0 holds the parameters
-    the call started from."""
-    import torch
-    from rl_rocket_amd.rollout import _policy_tensors
-
-    kw = dict(ent_weight=ent_weight, l2_weight=l2_weight)
-    ref64, st64 = R.reference(pol0, obs, acts, idx, torch.float64, **kw)
-    ref32, st32 = R.reference(pol0, obs, acts, idx, torch.float32, **kw)
-    for name, a, r, t, w in zip(P.NAMES, grads, ref64, ref32, _policy_tensors(pol0)):
-        a = a.double()
-        scale = r.abs().max().item()
-        err, err32 = (a - r).abs().max().item(), (t - r).abs().max().item()
-        print("%s %-9s max|ref| %.3e  fused err %.2e  torch-fp32 err %.2e" % (label, name, scale, err, err32))
-        assert bool(torch.isfinite(a).all()), name
-        assert err <= 1e-4 * scale + 1e-7, (name, err, scale, err32)
-        if name in P.VF_NAMES:
-            if l2_weight == 0.0:
-                assert torch.count_nonzero(a).item() == 0, name
-            else:  # l2_weight (as the fp32 argument it is) times w, within one fp32 rounding
-                want = float(np.float32(l2_weight)) * w.detach().double()
-                assert bool(((a - want).abs() <= 2.0 ** -24 * want.abs()).all()), name
-    st = stats.tolist()
-    assert all(v == v and abs(v) != float("inf") for v in st), st
-    assert st[7] == 0.0
-    for name, a, r, t in zip(R.STATS, st, st64, st32):
-        print("%s %-13s fp64 %.9e  fused err %.2e  torch-fp32 err %.2e" % (label, name, r, abs(a - r), abs(t - r)))
-        assert abs(a - r) <= 1e-5 * abs(r) + 1e-6, (name, a, r)
+_H = BcHelpers(R, P.NAMES, P.VF_NAMES, "rr_bc_update", lambda: R.sweep_inputs(14, 3))
+_minibatch, _adam, _one_call, _check_against_fp64, _state, _epoch = (
+    _H.minibatch, _H.adam, _H.one_call, _H.check_against_fp64, _H.state, _H.epoch)
 
 
 # 16 385: one past kMaxWG workgroups x 4 waves x 32 samples, a wave's second tile
@@ -201,64 +150,6 @@ def test_bc_optimizer_half_matches_float64_adam():
     assert all(float(opt.state[t]["step"]) == 6.0 for t in tensors) and len(tensors) == 13
 
 
-def _state(pol, opt):
-    import torch
-    from rl_rocket_amd.rollout import _policy_tensors
-
-    torch.cuda.synchronize()
-    out = []
-    for t in _policy_tensors(pol):
-        out += [t.detach().clone(), t.grad.clone(), opt.state[t]["exp_avg"].clone(), opt.state[t]["exp_avg_sq"].clone(),
-                opt.state[t]["step"].clone()]
-    return out
-
-
-def _epoch(mode, sizes=(4097, 4097, 130)):
-    """One epoch of minibatches (the last shorter: 33, 33 and 2 workgroups) on a copy of the sweep
-    policy: 'packed' every call packs for itself, 'chained' all but the first are chained, 'graph'
-    the chained epoch captured once and replayed once."""
-    import torch
-    from rl_rocket_amd.bc import BCUpdate, Demonstrations
-
-    pol0, obs, acts = R.sweep_inputs(14, 3)
-    pol = copy.deepcopy(pol0)
-    opt = _adam(pol)
-    step = BCUpdate(pol, opt, Demonstrations(obs, acts), max(sizes), ent_weight=0.01, l2_weight=1e-3)
-    perm = torch.randperm(N_ROWS, generator=torch.Generator().manual_seed(31)).cuda()
-    cuts = np.cumsum((0,) + tuple(sizes))
-    mbs = [perm[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
-    stats = []
-
-    def run():
-        for k, idx in enumerate(mbs):
-            stats.append(step(idx, chained=mode != "packed" and k > 0).clone())
-
-    if mode == "graph":
-        start = _state(pol, opt)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            run()  # warm-up outside the capture, then back to the start
-        torch.cuda.current_stream().wait_stream(side)
-        from rl_rocket_amd.rollout import _policy_tensors
-        with torch.no_grad():
-            it = iter(start)
-            for t in _policy_tensors(pol):
-                for dst in (t, t.grad, opt.state[t]["exp_avg"], opt.state[t]["exp_avg_sq"], opt.state[t]["step"]):
-                    dst.copy_(next(it))
-        del stats[:]
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            run()
-        with torch.no_grad():  # the capture ran nothing: still the start
-            for a, b in zip(_state(pol, opt), start):
-                assert torch.equal(a, b)
-        graph.replay()
-    else:
-        run()
-    return _state(pol, opt), [s.clone() for s in stats]
-
-
 def test_bc_same_call_twice_gives_the_same_bits():
     import torch
 
@@ -312,6 +203,58 @@ def test_bc_chained_epoch_is_bitwise_the_packed_and_the_replayed_one():
     for a, c in zip(st_p, st_g):
         assert torch.equal(a, c)
     assert float(packed[4]) == 3.0
+
+
+CARVING = [("gauss", 14, 3), ("gauss", 7, 2), ("cat", 7, 2), ("cat", 7, 4)]
+
+
+@pytest.mark.parametrize("bs", [33, 129])  # one workgroup, two
+@pytest.mark.parametrize("head,ns,na", CARVING, ids=["14-3", "7-2", "K2", "K4"])
+def test_bc_workspace_carving_leaves_the_tail_and_reads_no_state(head, ns, na, bs):
+    """Both calls through the C ABI on a workspace that is the first `bytes` of a larger buffer: one
+    unchained call, then one chained call. The 256 floats after the workspace keep their bit pattern, and
+    parameters, gradients, Adam state and both calls' statistics are bitwise those of the same two calls on
+    a workspace pre-filled with 0xFF bytes (NaNs): an unchained call reads no state from the workspace, and
+    the host's sections (images | finish sums | sink | partial vectors) lie inside the size the
+    *_workspace_size call returned."""
+    import ctypes
+
+    import bc_discrete_ref
+    import torch
+    from rl_rocket_amd import _lib
+    from rl_rocket_amd.bc import BCUpdate, Demonstrations
+
+    cat = head == "cat"
+    pol0, obs, acts = bc_discrete_ref.sweep_inputs(na) if cat else R.sweep_inputs(ns, na)
+    call = "rr_bc_update_discrete" if cat else "rr_bc_update"
+    rows = obs.shape[0]  # the two references' demonstrations differ in length
+    idx = [_minibatch(bs, n=rows), _minibatch(bs + 1, n=rows)[1:].contiguous()]
+    assert all(int(ix.max()) < rows and ix.numel() == bs for ix in idx)
+    tail = (0x5A5A0000 + torch.arange(256, dtype=torch.int32)).to(DEV)
+    out = []
+    for fill in (0x00, 0xFF):
+        pol = copy.deepcopy(pol0)
+        opt = _adam(pol)
+        s = BCUpdate(pol, opt, Demonstrations(obs, acts), bs, 0.01, 1e-3)
+        assert s._call == call and s._nbytes % 16 == 0
+        buf = torch.full((s._nbytes + 4 * 256,), fill, dtype=torch.uint8, device=DEV)
+        assert buf.data_ptr() % 16 == 0
+        buf[s._nbytes:].view(torch.int32).copy_(tail)
+        stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stats = []
+        for flags, ix in zip((0, _lib.RR_BC_CHAINED), idx):
+            _lib.check(getattr(s._lib, call)(ns, na, s._params_w, s._dst, s._m, s._v, s._s, obs.data_ptr(),
+                                             acts.data_ptr(), ix.data_ptr(), bs, 0.01, 1e-3, s.lr.data_ptr(), 0.9,
+                                             0.999, 1e-8, s.stats.data_ptr(), flags, buf.data_ptr(), s._nbytes,
+                                             stream), call)
+            stats.append(s.stats.clone())
+        out.append((_state(pol, opt) + stats, buf[s._nbytes:].view(torch.int32).clone()))
+    (a, ta), (b, tb) = out
+    assert torch.equal(ta, tail) and torch.equal(tb, tail)
+    assert len(a) == len(b) == 5 * (12 if cat else 13) + 2
+    for x, y in zip(a, b):
+        assert bool(torch.isfinite(x).all()) and torch.equal(x, y)
+    assert float(a[4]) == 2.0 and not torch.equal(a[-1], a[-2])
 
 
 def test_bc_chained_misuse_is_refused():

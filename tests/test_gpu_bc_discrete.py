@@ -30,70 +30,17 @@ import pytest
 import bc_discrete_ref as R
 import bc_ref
 import discrete_ref as D
+from bc_gpu_common import BcHelpers
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 N_ROWS = R.N_ROWS
 
-
-def _minibatch(bs, extra=0, n=N_ROWS):
-    import torch
-
-    g = torch.Generator().manual_seed(bs)
-    return torch.randperm(n, generator=g)[:bs + extra].contiguous().cuda()
-
-
-def _adam(pol, lr=1e-3, **kw):
-    import torch
-
-    return torch.optim.Adam(pol.parameters(), lr=lr, capturable=True, **kw)
-
-
-def _one_call(pol0, obs, acts, idx, ent_weight=1e-3, l2_weight=0.0):
-    """A copy of pol0 after one rr_bc_update_discrete on idx: (policy, its gradients fp32, the 8 stats)."""
-    import torch
-    from rl_rocket_amd.bc import BCUpdate, Demonstrations
-    from rl_rocket_amd.rollout import _policy_tensors
-
-    pol = copy.deepcopy(pol0)
-    step = BCUpdate(pol, _adam(pol), Demonstrations(obs, acts), idx.numel(), ent_weight, l2_weight)
-    assert step._call == "rr_bc_update_discrete" and len(step.params) == 12
-    stats = step(idx).clone()
-    torch.cuda.synchronize()
-    return pol, [t.grad.clone() for t in _policy_tensors(pol)], stats
-
-
-def _check_against_fp64(label, pol0, obs, acts, idx, grads, stats, ent_weight=1e-3, l2_weight=0.0):
-    """The learner's bars on the gradients a call left and its statistics; pol0 holds the parameters the
-    call started from. Returns the float64 figures."""
-    import torch
-    from rl_rocket_amd.rollout import _policy_tensors
-
-    kw = dict(ent_weight=ent_weight, l2_weight=l2_weight)
-    ref64, st64 = R.reference(pol0, obs, acts, idx, torch.float64, **kw)
-    ref32, st32 = R.reference(pol0, obs, acts, idx, torch.float32, **kw)
-    assert len(grads) == len(ref64) == 12
-    for name, a, r, t, w in zip(R.NAMES, grads, ref64, ref32, _policy_tensors(pol0)):
-        a = a.double()
-        scale = r.abs().max().item()
-        err, err32 = (a - r).abs().max().item(), (t - r).abs().max().item()
-        print("%s %-9s max|ref| %.3e  fused err %.2e  torch-fp32 err %.2e" % (label, name, scale, err, err32))
-        assert a.shape == w.shape and bool(torch.isfinite(a).all()), name
-        assert err <= 1e-4 * scale + 1e-7, (name, err, scale, err32)
-        if name in R.VF_NAMES:
-            if l2_weight == 0.0:
-                assert torch.count_nonzero(a).item() == 0, name
-            else:  # l2_weight (as the fp32 argument it is) times w, within one fp32 rounding
-                want = float(np.float32(l2_weight)) * w.detach().double()
-                assert bool(((a - want).abs() <= 2.0 ** -24 * want.abs()).all()), name
-    st = stats.tolist()
-    assert all(v == v and abs(v) != float("inf") for v in st), st
-    assert st[7] == 0.0
-    for name, a, r, t in zip(R.STATS, st, st64, st32):
-        print("%s %-13s fp64 %.9e  fused err %.2e  torch-fp32 err %.2e" % (label, name, r, abs(a - r), abs(t - r)))
-        assert abs(a - r) <= 1e-5 * abs(r) + 1e-6, (name, a, r)
-    return st64
+# one_call asserts step._call and len(step.params) == 12; check_against_fp64 that a.shape == w.shape
+_H = BcHelpers(R, R.NAMES, R.VF_NAMES, "rr_bc_update_discrete", lambda: R.sweep_inputs(4))
+_minibatch, _adam, _one_call, _check_against_fp64, _state, _epoch = (
+    _H.minibatch, _H.adam, _H.one_call, _H.check_against_fp64, _H.state, _H.epoch)
 
 
 # K = 4: the minimum, the 32-sample tile's edges, one past a workgroup, 33 workgroups, one past kMaxWG
@@ -231,64 +178,6 @@ def test_optimizer_half_matches_float64_adam():
             assert torch.allclose(st["exp_avg_sq"].double(), v, rtol=1e-5, atol=1e-12), name
             assert not torch.equal(t.detach(), before[R.NAMES.index(name)]), name
     assert all(float(opt.state[t]["step"]) == 6.0 for t in tensors) and len(tensors) == 12
-
-
-def _state(pol, opt):
-    import torch
-    from rl_rocket_amd.rollout import _policy_tensors
-
-    torch.cuda.synchronize()
-    out = []
-    for t in _policy_tensors(pol):
-        out += [t.detach().clone(), t.grad.clone(), opt.state[t]["exp_avg"].clone(), opt.state[t]["exp_avg_sq"].clone(),
-                opt.state[t]["step"].clone()]
-    return out
-
-
-def _epoch(mode, sizes=(4097, 4097, 130)):
-    """One epoch of minibatches (the last shorter: 33, 33 and 2 workgroups) on a copy of the K = 4 sweep
-    policy: 'packed' every call packs for itself, 'chained' all but the first are chained, 'graph' the
-    chained epoch captured once and replayed once."""
-    import torch
-    from rl_rocket_amd.bc import BCUpdate, Demonstrations
-    from rl_rocket_amd.rollout import _policy_tensors
-
-    pol0, obs, acts = R.sweep_inputs(4)
-    pol = copy.deepcopy(pol0)
-    opt = _adam(pol)
-    step = BCUpdate(pol, opt, Demonstrations(obs, acts), max(sizes), ent_weight=0.01, l2_weight=1e-3)
-    perm = torch.randperm(N_ROWS, generator=torch.Generator().manual_seed(31)).cuda()
-    cuts = np.cumsum((0,) + tuple(sizes))
-    mbs = [perm[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
-    stats = []
-
-    def run():
-        for k, idx in enumerate(mbs):
-            stats.append(step(idx, chained=mode != "packed" and k > 0).clone())
-
-    if mode == "graph":
-        start = _state(pol, opt)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            run()  # warm-up outside the capture, then back to the start
-        torch.cuda.current_stream().wait_stream(side)
-        with torch.no_grad():
-            it = iter(start)
-            for t in _policy_tensors(pol):
-                for dst in (t, t.grad, opt.state[t]["exp_avg"], opt.state[t]["exp_avg_sq"], opt.state[t]["step"]):
-                    dst.copy_(next(it))
-        del stats[:]
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            run()
-        with torch.no_grad():  # the capture ran nothing: still the start
-            for a, b in zip(_state(pol, opt), start):
-                assert torch.equal(a, b)
-        graph.replay()
-    else:
-        run()
-    return _state(pol, opt), [s.clone() for s in stats]
 
 
 def test_same_call_twice_gives_the_same_bits():

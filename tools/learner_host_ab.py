@@ -2,7 +2,7 @@
 """Host overhead of the fused learner calls in this tree beside another tree (the parent commit,
 exported and built somewhere), measured in one session with the trees alternating.
 
-    python tools/learner_host_ab.py --parent DIR [--rounds 3] [--out FILE]
+    python tools/learner_host_ab.py --parent DIR [--rounds 3] [--eager-only] [--out FILE]
 
 The kernels of the two trees are the same machine code (tools/isa_diff.py), so what can differ is the
 Python and C++ host path of a call. Every round runs, in each tree in turn (the parent first), three
@@ -11,9 +11,11 @@ children with that tree as working directory:
             training iteration (ms)
   bc_ab     tools/bc_ab.py: the chained 65 536-row rr_bc_update / rr_ppo_update minibatch in a graph
             replay (us)
-  eager     this file with --child: PPOUpdate.__call__, BCUpdate.__call__ and PPOUpdateDiscrete.__call__
-            (3DOF, 4 choices) called eagerly at batch 64, where the host path dominates: 7 runs of
-            2000 calls between two synchronises on the host clock, the median run (us per call)
+  eager     this file with --child: PPOUpdate.__call__, BCUpdate.__call__ and, for the Categorical policy
+            (3DOF, 4 choices), PPOUpdateDiscrete.__call__ and BCUpdate.__call__, called eagerly at batch
+            64, where the host path dominates: 7 runs of 2000 calls between two synchronises on the host
+            clock, the median run (us per call)
+--eager-only runs the third child alone (a change that touches only the C++ host path of a call).
 The bar is the parent's own run-to-run spread (max - min over its rounds): this tree's median over
 the rounds may not lie above the parent's median by more than that. The record holds every raw
 number. A child that fails or exceeds its time limit ends the measurement.
@@ -32,8 +34,8 @@ BENCH = ["bench.py", "--gpus", "1", "--mode", "rollout", "--full", "--steps", "2
 
 
 def child():
-    """us per eager call of PPOUpdate, BCUpdate and PPOUpdateDiscrete at batch 64, from the tree in the
-    working directory."""
+    """us per eager call of PPOUpdate, BCUpdate and the Categorical policy's two at batch 64, from the tree
+    in the working directory."""
     sys.path.insert(0, os.getcwd())
     import types
 
@@ -57,11 +59,12 @@ def child():
                                  actions=torch.randint(0, 4, (1, m, 1), device=dev, generator=g).float(),
                                  log_probs=ro.log_probs, advantages=ro.advantages, returns=ro.returns)
     out = {}
-    for name in ("ppo_update_call_us", "bc_update_call_us", "ppo_update_discrete_call_us"):
+    for name in ("ppo_update_call_us", "bc_update_call_us", "ppo_update_discrete_call_us", "bc_update_discrete_call_us"):
         pol = (MlpCategoricalActorCritic(7, 4) if "discrete" in name else MlpActorCritic(ns, na)).to(dev)
         opt = torch.optim.Adam(pol.parameters(), lr=1e-4, capturable=True)
-        step = (PPOUpdateDiscrete(pol, opt, ro_d, bs) if "discrete" in name else
+        step = (PPOUpdateDiscrete(pol, opt, ro_d, bs) if name.startswith("ppo_update_d") else
                 PPOUpdate(pol, opt, ro, bs) if name.startswith("ppo") else
+                BCUpdate(pol, opt, Demonstrations(ro_d.obs[0], ro_d.actions[0]), bs) if "discrete" in name else
                 BCUpdate(pol, opt, Demonstrations(obs, acts), bs))
         runs = []
         for _ in range(8):  # the first run warms up
@@ -84,18 +87,19 @@ def run(cmd, cwd, limit):
     return json.loads([line for line in p.stdout.splitlines() if line.startswith("{")][-1])
 
 
-def measure(tree):
+def measure(tree, eager_only=False):
+    e = run([os.path.abspath(__file__), "--child"], tree, 300)
+    eager = {"eager_" + k: v["median"] for k, v in e.items()}
+    if eager_only:
+        return dict(eager, raw={"eager": e})
     b = run(BENCH, tree, 300)
     a = run([os.path.join("tools", "bc_ab.py"), "--runs", "5"], tree, 300)
-    e = run([os.path.abspath(__file__), "--child"], tree, 300)
     upd = b["ppo_update"]
     return {"bench_eager_epoch_ms": upd["eager_epoch_ms"], "bench_graphed_epoch_ms": upd["graphed_epoch_ms"],
             "bench_fused_graphed_epoch_ms": upd["fused_graphed_epoch_ms"],
             "bench_train_iteration_ms": b["train_iteration"]["ms_per_iteration"],
             "bc_ab_bc_minibatch_us": a["bc"]["median"], "bc_ab_ppo_minibatch_us": a["ppo"]["median"],
-            "eager_ppo_update_call_us": e["ppo_update_call_us"]["median"],
-            "eager_bc_update_call_us": e["bc_update_call_us"]["median"],
-            "eager_ppo_update_discrete_call_us": e["ppo_update_discrete_call_us"]["median"],
+            **eager,
             "raw": {"bench_ppo_update": upd, "bench_train_iteration": b["train_iteration"]["ms_per_iteration"],
                     "bc_ab": {k: a[k] for k in ("bc", "ppo")}, "eager": e}}
 
@@ -104,6 +108,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", help="the other tree: an export of the parent commit with its library built")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--eager-only", action="store_true", help="only the eager calls' host cost")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -124,14 +129,15 @@ def main():
 
     for _ in range(args.rounds):
         for k, tree in trees.items():
-            rounds[k].append(measure(tree))
+            rounds[k].append(measure(tree, args.eager_only))
             write()  # what has been measured so far, should a later child end the run
     verdict = {}
     for m in [k for k in rounds["this"][0] if k != "raw"]:
         par, new = [r[m] for r in rounds["parent"]], [r[m] for r in rounds["this"]]
         spread = max(par) - min(par)
         verdict[m] = {"parent": par, "this": new, "parent_median": statistics.median(par),
-                      "this_median": statistics.median(new), "parent_spread": spread,
+                      "this_median": statistics.median(new), "parent_spread": spread, "parent_max": max(par),
+                      "this_range": [min(new), max(new)], "below_parent_max": statistics.median(new) <= max(par),
                       "within": statistics.median(new) - statistics.median(par) <= spread}
     rec["metrics"] = verdict
     rec["verdict"] = "within the parent's spread" if all(v["within"] for v in verdict.values()) else \
