@@ -799,6 +799,45 @@ int rr_bc_update_discrete(int obs_dim, int n_choices, float* const* params, floa
                           const float* lr, double beta1, double beta2, float eps, float* stats, uint32_t flags,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* The one-launch collect, its per-step form and the one-launch evaluation for this policy (pure
+ * additions to ABI 14: a caller that needs them looks the symbols up). The handle is a 3DOF one with
+ * an RK4 or Euler integrator, params an image of rr_policy_pack_discrete (16-B aligned), precision
+ * RR_POLICY_FP32, n_choices K in 2 .. 4 and table a HOST array [K][2] of finite floats, copied into the
+ * launch (rows past K are not read), as for rr_policy_act_discrete.
+ *
+ * rr_rollout_step_discrete / rr_rollout_collect_discrete are rr_rollout_step / rr_rollout_collect with
+ * the sample of rr_policy_act_discrete in place of the Gaussian one: the same key, one uniform draw,
+ * the inverse-CDF index; buf_action is [n] / [n_steps][n], ONE float per sample holding the index,
+ * buf_log_prob is log p_index and the env steps with table[index]. Everything else (env step, reward
+ * terms, TimeLimit, the timeout bootstrap, terminal rows, auto-reset, V(last obs), the fp64 GAE scan,
+ * the optional arguments, asynchrony and capture) is rr_rollout_step's / rr_rollout_collect's. Bitwise
+ * the rollout of n_steps x (rr_policy_act_discrete + rr_step) + rr_policy_bootstrap(7, 4) + rr_gae
+ * (tests/test_gpu_rollout_discrete.py).
+ *
+ * rr_policy_evaluate_discrete is rr_policy_evaluate with the action table[argmax_k<K z_k], the lowest
+ * index on a tie (SB3's deterministic prediction behind DiscreteActions3DOF); rows, max_steps, obs,
+ * asynchrony and capture are rr_policy_evaluate's.
+ *
+ * RR_EINVAL before any HIP call, with a message that starts with the function's name: a NULL handle
+ * or required buffer, a 6DOF handle, an RR_INT_DOPRI5 handle, a precision other than RR_POLICY_FP32,
+ * n_choices outside 2 .. 4, a NULL table or a non-finite entry in its first n_choices rows, params not
+ * 16-B aligned, and what rr_rollout_collect (n_steps <= 0, buf_advantage without buf_return) /
+ * rr_policy_evaluate (no RR_FLAG_AUTO_RESET, n_episodes < 1, no TimeLimit with max_steps 0, out or
+ * out->episodes NULL) refuse. */
+int rr_rollout_step_discrete(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                             uint64_t seed, const uint64_t* iter, int t, float gamma, float* buf_obs,
+                             float* buf_action, float* buf_value, float* buf_log_prob, float* buf_start,
+                             float* buf_reward, float* obs, float* reward, uint8_t* done, uint8_t* truncated,
+                             float* terms, void* stream);
+int rr_rollout_collect_discrete(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                                uint64_t seed, const uint64_t* iter, int n_steps, double gamma, double gae_lambda,
+                                float* buf_obs, float* buf_action, float* buf_value, float* buf_log_prob,
+                                float* buf_start, float* buf_reward, float* buf_advantage, float* buf_return,
+                                float* last_value, float* last_done, float* last_start, float* obs, float* reward,
+                                uint8_t* done, uint8_t* truncated, float* terms, void* stream);
+int rr_policy_evaluate_discrete(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                                int n_episodes, int64_t max_steps, const rr_eval_out* out, float* obs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

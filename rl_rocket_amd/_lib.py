@@ -236,6 +236,13 @@ SIGNATURES = {
     "rr_bc_update_discrete": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 8 +
                               [ctypes.c_int64, ctypes.c_float, ctypes.c_float, _P, ctypes.c_double, ctypes.c_double,
                                ctypes.c_float, _P, ctypes.c_uint32, _P, ctypes.c_int64, _P]),
+    # the Gaussian calls' arguments with (n_choices, table) after params
+    "rr_rollout_step_discrete": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_uint64, _P,
+                                                ctypes.c_int, ctypes.c_float] + [_P] * 12),
+    "rr_rollout_collect_discrete": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_uint64, _P,
+                                                   ctypes.c_int, ctypes.c_double, ctypes.c_double] + [_P] * 17),
+    "rr_policy_evaluate_discrete": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_int64, ctypes.POINTER(RrEvalOut), _P, _P]),
 }
 
 _LIB = None

@@ -1183,6 +1183,14 @@ struct CollectStatsIO {
     uint32_t rows;           // ceil(n / 64): the collect's live waves
 };
 static_assert(std::is_trivially_copyable_v<CollectStatsIO>, "CollectStatsIO crosses TUs by memcpy");
+// ... and the Categorical head of rollout_discrete/rocket_rollout_discrete.hip's kernels, beside the
+// collect's EnvLaunch / RolloutIO or the evaluation's EnvLaunch / EvalIO: the number of choices and
+// their [gimbal, thrust] rows (rows >= n_choices are zeros and never read)
+struct DiscHead {
+    int n_choices;
+    float table[4][2];
+};
+static_assert(std::is_trivially_copyable_v<DiscHead>, "DiscHead crosses TUs by memcpy");
 static_assert(std::is_trivially_copyable_v<EvalExactLaunch>, "EvalExactLaunch crosses TUs by memcpy");
 static_assert(std::is_trivially_copyable_v<EnvLaunch>, "EnvLaunch crosses TUs by memcpy");
 static_assert(std::is_trivially_copyable_v<ExactLaunch>, "ExactLaunch crosses TUs by memcpy");
@@ -1221,4 +1229,9 @@ __attribute__((visibility("hidden"))) int rrc_launch_bc(const void* launch, void
 __attribute__((visibility("hidden"))) int rrc_launch_discrete(const void* launch, void* stream);
 // bc_discrete/rocket_bc_discrete.hip: rr_bc_update_discrete's launches, a BcLaunch with n_choices and a sink
 __attribute__((visibility("hidden"))) int rrc_launch_bc_discrete(const void* launch, void* stream);
+// rollout_discrete/rocket_rollout_discrete.hip: the Categorical policy's one-launch collect (multi != 0),
+// its per-step launch and its one-launch evaluation; head points to the caller's DiscHead
+__attribute__((visibility("hidden"))) int rrc_launch_rollout_discrete(const void* launch, const void* io, const void* head,
+                                                                      int multi);
+__attribute__((visibility("hidden"))) int rrc_launch_eval_discrete(const void* launch, const void* io, const void* head);
 }

@@ -11,9 +11,18 @@
 // RR_EVAL_TRACE 1 selects the five regions that record the envs with a trace slot: the slot's load,
 // the recording lanes' setup with row 0 of episode 0, the step's record, row 0 of the next episode,
 // and the length of an episode cut by max_steps.
+// RR_DISCRETE_HEAD defined (rollout_discrete/rocket_rollout_discrete.hip: eval_discrete_kernel, which fixes
+// MODEL 3 and PREC 0 and adds the arguments n_choices and tab, a DiscTable) selects the Categorical
+// head: the pi tower's NH = 4 heads are logits and the action is the table row of the largest of the
+// first n_choices. Not defined: the Gaussian head's clipped means.
     constexpr int NS = Dims<MODEL>::NS, NA = Dims<MODEL>::NA, NT = Dims<MODEL>::NT, EV = Dims<MODEL>::EV;
     constexpr int EPW = rol::Shape<2>::kEPW, NWV = rol::Shape<2>::kWaves;
-    using L = pol::Layout<NS, NA, PREC>;
+#ifdef RR_DISCRETE_HEAD
+    constexpr int NH = 4;   // heads of the packed image (rr_policy_pack_discrete): the logits
+#else
+    constexpr int NH = NA;  // heads: the action means
+#endif
+    using L = pol::Layout<NS, NH, PREC>;
     __shared__ __attribute__((aligned(16))) float sp[L::SIZE];
     __shared__ __attribute__((aligned(16))) float tile_all[NWV][EPW * NS];  // the post-call obs rows (and the trace's lane words)
     __shared__ __attribute__((aligned(16))) rol::ResetParams<NS> rps;
@@ -43,7 +52,7 @@
 #if RR_EVAL_TRACE
     const uint32_t slot0 = bld_u(make_rsrc(tr0.slot, plane), vo, 0);  // the env's trace slot
 #endif
-    pol::stage_params<NS, NA, PREC, rol::Shape<2>::kThreads>(io.params, sp);
+    pol::stage_params<NS, NH, PREC, rol::Shape<2>::kThreads>(io.params, sp);
     rol::stage_reset<NS>(B.kp, &rps);
     const HotParams H = load_hot<NS>(P);
     const CounterLayout CL(P);
@@ -90,12 +99,27 @@
 
         // ---- deterministic action: the pi tower's means, clipped ----
         normalize_obs<NS>(y0, H.inv_norm, o);
-        float value, mean[NA], a_env[NA];
+        float value, mean[NH], a_env[NA];
         typename pol::XOp<PREC>::T x[2][L::KP1];
-        rol::regs_x<NS, NA, PREC>(o, x);
-        rol::policy_forward<NS, NA, PREC, 2, false>(sp, x, lane, value, mean);
+        rol::regs_x<NS, NH, PREC>(o, x);
+        rol::policy_forward<NS, NH, PREC, 2, false>(sp, x, lane, value, mean);
+#ifdef RR_DISCRETE_HEAD
+        // the most probable choice: the lowest q < n_choices with the largest logit (torch.argmax: on a tie
+        // the lowest index; a zero-packed head >= n_choices never wins), then its table row by compares
+        float zb = mean[0];
+        a_env[0] = tab.v[0][0];
+        a_env[1] = tab.v[0][1];
+#pragma unroll
+        for (int q = 1; q < NH; ++q)
+            if (q < n_choices && mean[q] > zb) {
+                zb = mean[q];
+                a_env[0] = tab.v[q][0];
+                a_env[1] = tab.v[q][1];
+            }
+#else
 #pragma unroll
         for (int a = 0; a < NA; ++a) a_env[a] = fminf(1.0f, fmaxf(-1.0f, mean[a]));
+#endif
 
         if (active) {
             // ---- env step (rollout_step_kernel / step_kernel) ----

@@ -382,6 +382,8 @@ __attribute__((weak)) int rrc_launch_learner_opts(const void*, void*) { return k
 __attribute__((weak)) int rrc_launch_bc(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_discrete(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_bc_discrete(const void*, void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_rollout_discrete(const void*, const void*, const void*, int) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_eval_discrete(const void*, const void*, const void*) { return kNoUnit; }
 }
 
 namespace {
@@ -1423,7 +1425,8 @@ int rr_policy_bootstrap(const float* params, int obs_dim, int act_dim, int preci
 
 namespace {
 int launch_rollout(rr_env* e, const char* who, bool multi, const float* params, int precision, uint64_t seed,
-                   const uint64_t* iter, RolloutIO& io, void* stream, const CollectStatsIO* stats = nullptr)
+                   const uint64_t* iter, RolloutIO& io, void* stream, const CollectStatsIO* stats = nullptr,
+                   const DiscHead* head = nullptr)
 {
     const std::string w = std::string(who) + ": ";
     if (!params || !iter || !io.buf_obs || !io.buf_act || !io.buf_val || !io.buf_logp || !io.buf_start ||
@@ -1450,7 +1453,9 @@ int launch_rollout(rr_env* e, const char* who, bool multi, const float* params, 
     // The collect kernel (MULTI) lives in the third translation unit (rocket_collect.hip), compiled
     // with the MFMA accumulators in VGPRs (rl_rocket_amd/build.py COLLECT_FLAGS).
     hipError_t err = hipSuccess;
-    if (multi && stats) {  // rr_rollout_collect_stats (collect_stats/rocket_collect_stats.hip): two launches
+    if (head) {  // the Categorical head (rollout_discrete/rocket_rollout_discrete.hip): the collect or one step
+        err = (hipError_t)rrc_launch_rollout_discrete(&L, &io, head, multi);
+    } else if (multi && stats) {  // rr_rollout_collect_stats (collect_stats/rocket_collect_stats.hip): two launches
         err = (hipError_t)rrc_launch_collect_stats(&L, &io, stats);
     } else if (multi) {
         err = (hipError_t)rrc_launch_collect(&L, &io);
@@ -1575,7 +1580,7 @@ namespace {
 // kernel's EvalIO and the launch. `who` prefixes every message.
 int evaluate(rr_env* e, const char* who, const float* params, int precision, int n_episodes, int64_t max_steps,
              const rr_eval_out* out, bool traced, const rr_eval_trace* trace, float* obs, void* stream,
-             bool exact = false)
+             bool exact = false, const DiscHead* head = nullptr)
 {
     const std::string w = std::string(who) + ": ";
     if (!e) return fail(RR_EINVAL, w + "null handle");
@@ -1619,7 +1624,9 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
     // the fast modes' kernels are compiled in the collect translation units (rocket_collect.hip,
     // eval_trace/), as the collect kernel they derive from
     hipError_t err;
-    if (exact) {
+    if (head) {  // rr_policy_evaluate_discrete (rollout_discrete/rocket_rollout_discrete.hip)
+        err = (hipError_t)rrc_launch_eval_discrete(&L, &io, head);
+    } else if (exact) {
         // eval_exact_kernel (eval_exact/rocket_eval_exact.hip): eval_kernel's grid, one variant for every N
         const EvalExactLaunch X = {e->p.model, prec, L.grid, e->d_xp, &b, e->state64, stream};
         err = (hipError_t)rrx_launch_eval_exact(&X, &io);
@@ -2156,6 +2163,96 @@ int rr_policy_act_discrete(const float* params, int obs_dim, int n_choices, cons
     D.start_out = start_out;
     const hipError_t err = (hipError_t)rrc_launch_discrete(&D, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_policy_act_discrete: launch");
+}
+
+namespace {
+// What rr_rollout_step_discrete, rr_rollout_collect_discrete and rr_policy_evaluate_discrete check besides
+// their Gaussian twins' checks, before any HIP call. The arguments first, so that they are refused
+// whatever the handle is, then the handle; `H` receives the kernels' head.
+int disc_head_args(const char* who, const float* params, int n_choices, const float* table, int precision, DiscHead& H)
+{
+    if (precision != RR_POLICY_FP32) return refuse(who, "precision must be RR_POLICY_FP32");
+    if (n_choices < 2 || n_choices > 4) return refuse(who, "n_choices must be in 2 .. 4");
+    if (!table) return refuse(who, "table must not be null");
+    H = {};
+    H.n_choices = n_choices;
+    for (int k = 0; k < n_choices; ++k)
+        for (int c = 0; c < 2; ++c) {
+            if (!std::isfinite(table[2 * k + c])) return refuse(who, "table entries must be finite");
+            H.table[k][c] = table[2 * k + c];
+        }
+    if (!params) return refuse(who, "params must not be null");
+    if (((uintptr_t)params & 15) != 0) return refuse(who, "params must be 16-B aligned");
+    return RR_OK;
+}
+int disc_handle_ok(const char* who, const rr_env* e)
+{
+    if (!e) return refuse(who, "null handle");
+    if (e->p.model != RR_MODEL_3DOF)
+        return refuse(who, "a 6DOF handle is refused: the table rows are [gimbal, thrust] of the 3DOF env");
+    if (e->p.integrator == RR_INT_DOPRI5)
+        return refuse(who, "RR_INT_DOPRI5 envs step through rr_policy_act_discrete + rr_step");
+    return RR_OK;
+}
+int disc_rollout_bufs_ok(const char* who, const uint64_t* iter, const RolloutIO& io)
+{
+    if (!iter || !io.buf_obs || !io.buf_act || !io.buf_val || !io.buf_logp || !io.buf_start || !io.buf_rew ||
+        !io.reward || !io.done)
+        return refuse(who, "null argument");
+    return RR_OK;
+}
+}  // namespace
+
+int rr_rollout_step_discrete(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                             uint64_t seed, const uint64_t* iter, int t, float gamma, float* buf_obs,
+                             float* buf_action, float* buf_value, float* buf_log_prob, float* buf_start,
+                             float* buf_reward, float* obs, float* reward, uint8_t* done, uint8_t* truncated,
+                             float* terms, void* stream)
+{
+    const char* who = "rr_rollout_step_discrete";
+    DiscHead H;
+    if (const int rc = disc_head_args(who, params, n_choices, table, precision, H); rc != RR_OK) return rc;
+    RolloutIO io = rollout_io(buf_obs, buf_action, buf_value, buf_log_prob, buf_start, buf_reward, obs, reward, done,
+                              truncated, terms);
+    if (const int rc = disc_rollout_bufs_ok(who, iter, io); rc != RR_OK) return rc;
+    if (const int rc = disc_handle_ok(who, e); rc != RR_OK) return rc;
+    io.t = (uint32_t)t;
+    io.gamma = gamma;
+    io.T = 1;
+    return launch_rollout(e, who, false, params, precision, seed, iter, io, stream, nullptr, &H);
+}
+
+int rr_rollout_collect_discrete(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                                uint64_t seed, const uint64_t* iter, int n_steps, double gamma, double gae_lambda,
+                                float* buf_obs, float* buf_action, float* buf_value, float* buf_log_prob,
+                                float* buf_start, float* buf_reward, float* buf_advantage, float* buf_return,
+                                float* last_value, float* last_done, float* last_start, float* obs, float* reward,
+                                uint8_t* done, uint8_t* truncated, float* terms, void* stream)
+{
+    const char* who = "rr_rollout_collect_discrete";
+    DiscHead H;
+    if (const int rc = disc_head_args(who, params, n_choices, table, precision, H); rc != RR_OK) return rc;
+    if (n_steps <= 0) return refuse(who, "n_steps must be positive");
+    if ((buf_advantage == nullptr) != (buf_return == nullptr))
+        return refuse(who, "buf_advantage and buf_return go together");
+    RolloutIO io = rollout_io(buf_obs, buf_action, buf_value, buf_log_prob, buf_start, buf_reward, obs, reward, done,
+                              truncated, terms);
+    if (const int rc = disc_rollout_bufs_ok(who, iter, io); rc != RR_OK) return rc;
+    if (const int rc = disc_handle_ok(who, e); rc != RR_OK) return rc;
+    collect_io(io, n_steps, gamma, gae_lambda, buf_advantage, buf_return, last_value, last_done, last_start);
+    return launch_rollout(e, who, true, params, precision, seed, iter, io, stream, nullptr, &H);
+}
+
+int rr_policy_evaluate_discrete(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                                int n_episodes, int64_t max_steps, const rr_eval_out* out, float* obs, void* stream)
+{
+    const char* who = "rr_policy_evaluate_discrete";
+    DiscHead H;
+    if (const int rc = disc_head_args(who, params, n_choices, table, precision, H); rc != RR_OK) return rc;
+    if (!out || !out->episodes) return refuse(who, "params, out and out->episodes must not be null");
+    if (n_episodes < 1) return refuse(who, "n_episodes must be at least 1");
+    if (const int rc = disc_handle_ok(who, e); rc != RR_OK) return rc;
+    return evaluate(e, who, params, precision, n_episodes, max_steps, out, false, nullptr, obs, stream, false, &H);
 }
 
 int rr_ppo_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes)

@@ -15,9 +15,19 @@
 // The RR_ST / RR_ACC_* stamp hooks (rocket_stamps.h) expand to nothing in the shipped library; in a
 // diagnostic build (RR_DIAG_STAMPS) the statistics kernel carries them too and, like the collect,
 // then overwrites io.last_value of each wave's first 16 envs.
+// RR_DISCRETE_HEAD defined (rollout_discrete/rocket_rollout_discrete.hip: rollout_discrete_kernel, which fixes
+// MODEL 3, PREC 0, NTW 2 and adds the arguments n_choices and tab, a DiscTable) selects the Categorical
+// head of the reference's DiscreteActions3DOF: the pi tower's NH = 4 heads are logits, of which the
+// first n_choices count, the sample region is discrete_act_kernel's (one uniform draw, the index, the
+// table row) and buf_act holds one float per sample, the index. Not defined: the Gaussian head.
     constexpr int NS = Dims<MODEL>::NS, NA = Dims<MODEL>::NA, NT = Dims<MODEL>::NT, EV = Dims<MODEL>::EV;
     constexpr int EPW = rol::Shape<NTW>::kEPW, NWV = rol::Shape<NTW>::kWaves;
-    using L = pol::Layout<NS, NA, PREC>;
+#ifdef RR_DISCRETE_HEAD
+    constexpr int NH = 4;   // heads of the packed image (rr_policy_pack_discrete): the logits
+#else
+    constexpr int NH = NA;  // heads: the action means
+#endif
+    using L = pol::Layout<NS, NH, PREC>;
     __shared__ __attribute__((aligned(16))) float sp[L::SIZE];
     __shared__ __attribute__((aligned(16))) float tile_all[NWV][EPW * NS];
     __shared__ __attribute__((aligned(16))) rol::ResetParams<NS> rps;
@@ -64,7 +74,7 @@
     float v0 = bld_f(st_r, vo, v0_off);
     float ret = (mode & RR_FLAG_EPISODE_STATS) ? bld_f(st_r, vo, ret_off) : 0.0f;
     bool start = io.done[ic] != 0;
-    pol::stage_params<NS, NA, PREC, rol::Shape<NTW>::kThreads>(io.params, sp);
+    pol::stage_params<NS, NH, PREC, rol::Shape<NTW>::kThreads>(io.params, sp);
     if (mode & RR_FLAG_AUTO_RESET) rol::stage_reset<NS>(B.kp, &rps);
     const HotParams H = load_hot<NS>(P);
     const CounterLayout CL(P);
@@ -91,13 +101,13 @@
 
         // ---- policy (rocket_policy.inc towers on two 32-env tiles; env = lane) ----
         const int half = lane >> 5;
-        float value, mean[NA];
+        float value, mean[NH];
         typename pol::XOp<PREC>::T x[NTW][L::KP1];
-        if constexpr (NTW == 2) rol::regs_x<NS, NA, PREC>(o, x);
-        else pol::load_x<NS, NA, PREC, NTW>(tile, lane, x);
+        if constexpr (NTW == 2) rol::regs_x<NS, NH, PREC>(o, x);
+        else pol::load_x<NS, NH, PREC, NTW>(tile, lane, x);
         RR_ST(0);
         // collect TU: the obs rows' buffer stores are issued after the value tower's layer-1 MFMAs
-        rol::policy_forward<NS, NA, PREC, NTW>(sp, x, lane, value, mean, [&](int p) {
+        rol::policy_forward<NS, NH, PREC, NTW>(sp, x, lane, value, mean, [&](int p) {
             if constexpr (kPolPrefetchA)
                 if (p == 1) rol::obs_end<NS, EPW>(obr, bobs_r, wave_base, lane);
             RR_ST(p);
@@ -107,6 +117,41 @@
         uint32_t key = mix32((uint32_t)(P.id_off + i) ^ io.seed_lo);
         key = mix32(key ^ (uint32_t)it ^ io.seed_hi);
         key = mix32(key ^ (uint32_t)(it >> 32) ^ (t * 0x9E3779B9u));
+#ifdef RR_DISCRETE_HEAD
+        // The Categorical head: discrete_act_kernel's lines (discrete/rocket_discrete.hip, the twin), statement
+        // for statement, so that the index, the log-prob and the table row have its bits. Softmax over the
+        // first n_choices logits; log p_k from the log of the sum (a p_k that underflows to 0 leaves log p_k
+        // finite)
+        float zm = mean[0];
+#pragma unroll
+        for (int q = 1; q < NH; ++q) zm = q < n_choices ? fmaxf(zm, mean[q]) : zm;
+        float ex[NH], sum = 0.0f;
+#pragma unroll
+        for (int q = 0; q < NH; ++q) {
+            ex[q] = q < n_choices ? expf(mean[q] - zm) : 0.0f;
+            sum += ex[q];
+        }
+        const float lse = logf(sum);
+        const float u = (float)(mix32(key) >> 8) * 0x1p-24f;  // one uniform per env, [0, 1)
+        // index = the number of q in 0 .. K - 2 whose running sum p_0 + .. + p_q is <= u
+        int index = 0;
+        float cdf = 0.0f;
+#pragma unroll
+        for (int q = 0; q < NH - 1; ++q) {
+            cdf += ex[q] / sum;
+            index += (q < n_choices - 1 && cdf <= u) ? 1 : 0;
+        }
+        // the chosen logit and the table row by compares: no data-dependent address
+        float za = mean[0], a_env[NA] = {tab.v[0][0], tab.v[0][1]};
+#pragma unroll
+        for (int q = 1; q < NH; ++q)
+            if (index == q) {
+                za = mean[q];
+                a_env[0] = tab.v[q][0];
+                a_env[1] = tab.v[q][1];
+            }
+        const float act[1] = {(float)index}, lp = (za - zm) - lse;
+#else
         float eps[NA];
 #pragma unroll
         for (int a = 0; a < NA; a += 2) {
@@ -122,6 +167,7 @@
             lp += -0.5f * eps[a] * eps[a] - ls - 0.918938533204672742f;
             a_env[a] = fminf(1.0f, fmaxf(-1.0f, act[a]));
         }
+#endif
 
         RR_ST(9);
         // ---- env step (step_kernel) ----
@@ -145,7 +191,7 @@
         float rb = r;
         if (__ballot(trunc && valid)) {
             rol::put_rows<NS, NTW>(tile, o, lane);
-            const float vt = rol::tile_value<NS, NA, PREC, NTW>(sp, tile, lane);
+            const float vt = rol::tile_value<NS, NH, PREC, NTW>(sp, tile, lane);
             rb = trunc ? fmaf(io.gamma, vt, r) : r;
         }
 
@@ -195,8 +241,12 @@
 
         // ---- rollout buffer slices of step k; env outputs of the last step ----
         if (valid) {
+#ifdef RR_DISCRETE_HEAD
+            io.buf_act[so + i] = act[0];  // [T][n]: the index as a float (SB3's buffer of a Discrete space)
+#else
 #pragma unroll
             for (int a = 0; a < NA; ++a) io.buf_act[(so + i) * NA + a] = act[a];
+#endif
             io.buf_val[so + i] = value;
             io.buf_logp[so + i] = lp;
             io.buf_start[so + i] = start ? 1.0f : 0.0f;
@@ -237,7 +287,7 @@
         // ---- end of the rollout: V(last obs) (rr_policy_bootstrap), the SB3 episode-start /
         // last-done flags and GAE (rr_gae) of this env ----
         rol::put_rows<NS, NTW>(tile, o, lane);
-        const float lv = rol::tile_value<NS, NA, PREC, NTW>(sp, tile, lane);
+        const float lv = rol::tile_value<NS, NH, PREC, NTW>(sp, tile, lane);
 #if RR_COLLECT_STATS
         double ss[4] = {0.0, 0.0, 0.0, 0.0};  // sum y, y^2, d, d^2 of this env's samples
 #endif

@@ -5,7 +5,7 @@ from ._lib import (RR_EVAL_BOUNDS as EVAL_BOUNDS, RR_EVAL_EVENT as EVAL_EVENT, R
                    RR_EVAL_NONFINITE as EVAL_NONFINITE, RR_EVAL_TRUNCATED as EVAL_TRUNCATED)
 from .eval_trace import EpisodeRecord, EvalTrace  # noqa: F401
 from .policy import (POLICY_PRECISIONS, MlpActorCritic, MlpCategoricalActorCritic, PolicyPack,
-                     fused_grad_supported)
+                     fused_discrete_supported, fused_grad_supported)
 
 
 class EvalResult:
@@ -90,10 +90,15 @@ class PolicyEvaluator:
     history takes v_0 from the first recorded state: reset first, as for whole episodes.
     ``record=None`` is the plain evaluation (``rr_policy_evaluate``).
 
-    A ``MlpCategoricalActorCritic`` (discrete 3DOF actions) runs through the step-by-step path
-    (``fused=False``, chosen automatically) with the action ``policy.continuous(policy.mode(logits))``,
-    SB3's deterministic prediction behind ``DiscreteActions3DOF``; ``fused=True`` and ``record=``
-    raise for it (there is no fused evaluation kernel with a Categorical head)."""
+    A ``MlpCategoricalActorCritic`` (discrete 3DOF actions) takes the action
+    ``policy.continuous(policy.mode(logits))``, SB3's deterministic prediction behind
+    ``DiscreteActions3DOF``. By default it runs through the step-by-step path (``fused=False``, chosen
+    automatically; the default stays there until a later change flips it). ``fused=True`` is opt-in:
+    ONE launch (``rr_policy_evaluate_discrete``: the evaluation kernel's loop with the argmax of the
+    logits, the lowest index on a tie, and the table row), on a CUDA batch with an RK4 / Euler
+    integrator, 64x64 towers and 2 .. 4 choices. Where two logits lie within the fp32 towers' error of
+    each other the two paths may pick different rows. ``record=`` and a ``policy_dtype`` other than
+    "fp32" raise for it."""
 
     def __init__(self, batch, policy, n_episodes=5, max_steps=None, policy_dtype="fp32", fused=None, record=None,
                  record_steps=None):
@@ -106,10 +111,22 @@ class PolicyEvaluator:
         if self._discrete:
             if ns != 7 or na != 2:
                 raise ValueError("a Categorical policy drives the 3DOF env (its table rows are [gimbal, thrust])")
-            if fused or record is not None:
-                raise ValueError("%s is not available for a Categorical policy: it is evaluated step by step "
-                                 "(fused=False), without recording" % ("fused=True" if fused else "record="))
-            fused = False
+            if record is not None:
+                raise ValueError("record= is not available for a Categorical policy: neither of its evaluation "
+                                 "paths records")
+            if policy_dtype != "fp32" and policy_dtype in POLICY_PRECISIONS:
+                raise ValueError("policy_dtype=%r is not available for a Categorical policy: it is evaluated on "
+                                 "fp32 towers" % policy_dtype)
+            if fused:  # the opt-in launch of the discrete-rollout unit
+                if torch.device(batch.device).type != "cuda":
+                    raise ValueError("fused=True for a Categorical policy needs a batch on a CUDA device "
+                                     "(rr_policy_evaluate_discrete)")
+                if not fused_discrete_supported(policy, ns):
+                    raise ValueError("fused=True needs a Categorical policy with 64x64 towers and 2 .. 4 choices")
+                if int(batch.params.integrator) == _lib.RR_INT_DOPRI5:
+                    raise ValueError("fused=True is not available for a Categorical policy on an "
+                                     "integrator=\"dopri5\" batch: it is evaluated step by step there")
+            fused = bool(fused)
         dev = batch.device
         p = batch.params
         if not p.flags & _lib.RR_FLAG_AUTO_RESET:
@@ -123,7 +140,7 @@ class PolicyEvaluator:
         dopri = int(p.integrator) == _lib.RR_INT_DOPRI5
         if fused is None:  # an exact-mode batch keeps the step-by-step path unless asked (fused=True)
             fused = fused_grad_supported(policy, ns, na) and not dopri
-        if fused and not fused_grad_supported(policy, ns, na):
+        if fused and not self._discrete and not fused_grad_supported(policy, ns, na):
             raise ValueError("fused evaluation needs an MlpActorCritic with 64x64 towers")
         if fused and dopri and record is not None:
             raise ValueError("record= on an integrator=\"dopri5\" batch needs fused=False (the one-launch exact "
@@ -148,7 +165,11 @@ class PolicyEvaluator:
                                  trace=self.trace)
         self._lib = _lib.load()
         if self.fused:
-            self._pack = PolicyPack(policy, ns, na, dev, precision=policy_dtype)
+            self._pack = PolicyPack(policy, ns, policy.n_choices if self._discrete else na, dev, precision=policy_dtype)
+            if self._discrete:  # the host table the call copies into its launch
+                import ctypes
+
+                self._table = (ctypes.c_float * (2 * policy.n_choices))(*policy.table.reshape(-1).tolist())
             self._out = _lib.RrEvalOut(*[t.data_ptr() for t in (self.episodes, self.ep_return, self.ep_length,
                                                                  self.flags, self.used_mass, self.final_state)])
             if self.trace is not None:
@@ -218,6 +239,12 @@ class PolicyEvaluator:
                                                           self.n_episodes, self.max_steps, ctypes.byref(self._out),
                                                           ctypes.byref(self._trace_io), _ptr(env.obs), stream),
                        "rr_policy_evaluate_trace")
+            return self.result
+        if self._discrete:
+            _lib.check(self._lib.rr_policy_evaluate_discrete(env._h, _ptr(self._pack.pack()), self.policy.n_choices,
+                                                             self._table, self._pack.prec, self.n_episodes,
+                                                             self.max_steps, ctypes.byref(self._out), _ptr(env.obs),
+                                                             stream), "rr_policy_evaluate_discrete")
             return self.result
         call, name = ((self._lib.rr_policy_evaluate_exact, "rr_policy_evaluate_exact") if self._exact else
                       (self._lib.rr_policy_evaluate, "rr_policy_evaluate"))

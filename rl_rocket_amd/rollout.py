@@ -57,11 +57,16 @@ class DeviceRollout:
 
     A ``MlpCategoricalActorCritic`` (the reference's ``DiscreteActions3DOF`` stack, 3DOF batches
     only): ``actions`` is [n_steps, N, 1], the chosen index as a float (SB3's buffer for a
-    ``Discrete`` space), and the env steps with the policy's table row. The fused path is the
+    ``Discrete`` space), and the env steps with the policy's table row. The default fused path is the
     two-launch one (``rr_policy_act_discrete`` + the env step, then ``rr_policy_bootstrap`` and
-    ``rr_gae``), so ``one_launch`` defaults to False; ``one_launch=True``, ``per_step=True``,
-    ``stats=True`` and a ``policy_dtype`` other than "fp32" raise. ``fused=False`` samples with
-    ``torch.multinomial`` on ``generator``."""
+    ``rr_gae``). ``one_launch=True`` is opt-in for it: the whole ``collect`` in ONE launch
+    (``rr_rollout_collect_discrete``: the collect kernel's loop with a softmax head, one uniform draw
+    per sample and the table row), and with ``per_step=True`` one ``rr_rollout_step_discrete`` per
+    step, then ``rr_policy_bootstrap`` and ``rr_gae``; both give bitwise the two-launch rollout. They
+    need a batch on a CUDA device, an RK4 / Euler integrator, 64x64 towers and 2 .. 4 choices.
+    ``one_launch`` stays False by default here (unlike the Gaussian policy's) until a later change
+    flips it. ``stats=True`` and a ``policy_dtype`` other than "fp32" raise. ``fused=False`` samples
+    with ``torch.multinomial`` on ``generator``."""
 
     def __init__(self, batch, policy, n_steps=16, gamma=0.99, gae_lambda=0.95, generator=None, fused=None,
                  seed=0, policy_dtype="fp32", one_launch=None, per_step=False, stats=False):
@@ -73,17 +78,26 @@ class DeviceRollout:
             if ns != 7 or na != 2:
                 raise ValueError("a Categorical policy drives the 3DOF env (its table rows are [gimbal, thrust]): "
                                  "a 6DOF batch is refused")
-            what = ("one_launch=True" if one_launch else "per_step=True" if per_step else "stats=True" if stats
-                    else "policy_dtype=%r" % policy_dtype if policy_dtype != "fp32" else None)
+            what = "stats=True" if stats else "policy_dtype=%r" % policy_dtype if policy_dtype != "fp32" else None
             if what:
-                raise ValueError("%s is not available for a Categorical policy: it collects with two launches per "
-                                 "step (rr_policy_act_discrete + the env step) on fp32 towers, and the one-launch "
-                                 "collect, rr_rollout_step and the collect statistics have no Categorical head" % what)
+                raise ValueError("%s is not available for a Categorical policy: it collects on fp32 towers, and "
+                                 "the collect statistics have no Categorical head" % what)
+            opt = "one_launch=True" if one_launch else "per_step=True" if per_step and one_launch is None else None
+            if opt:  # the opt-in launches of the discrete-rollout unit
+                if torch.device(batch.device).type != "cuda":
+                    raise ValueError("%s for a Categorical policy needs a batch on a CUDA device "
+                                     "(rr_rollout_collect_discrete / rr_rollout_step_discrete)" % opt)
+                if fused is not None and not fused:
+                    raise ValueError("%s needs the fused policy (fused=False collects in PyTorch ops)" % opt)
+                if int(batch.params.integrator) == 2:  # RR_INT_DOPRI5
+                    raise ValueError("%s is not available on an integrator=\"dopri5\" batch: a Categorical policy "
+                                     "collects there with two launches per step" % opt)
+                fused = True
             if fused and not fused_discrete_supported(policy, ns):
                 raise ValueError("the fused Categorical path needs 64x64 towers and 2 .. 4 choices")
             if fused is None:
                 fused = fused_discrete_supported(policy, ns)
-            one_launch = False
+            one_launch = bool(opt)
         dev = batch.device
         f = dict(device=dev, dtype=torch.float32)
         self.obs = torch.zeros((n_steps, n, ns), **f)
@@ -143,9 +157,13 @@ class DeviceRollout:
             # the two-launch path's act call (its symbol, the arguments between params and the precision)
             # and rr_policy_bootstrap's act_dim
             self._act, self._act_shape, self._boot_na = "rr_policy_act", (ns, na), na
-            if self.discrete:  # the host table rr_policy_act_discrete copies into its launch; the 4-head image's (7, 4)
+            # the one-launch and per-step calls, and what they take between params and the precision
+            self._collect, self._step, self._head = "rr_rollout_collect", "rr_rollout_step", ()
+            if self.discrete:  # the host table the discrete calls copy into their launch; the 4-head image's (7, 4)
                 table = (ctypes.c_float * (2 * policy.n_choices))(*policy.table.reshape(-1).tolist())
                 self._act, self._act_shape, self._boot_na = "rr_policy_act_discrete", (ns, policy.n_choices, table), 4
+                self._collect, self._step = "rr_rollout_collect_discrete", "rr_rollout_step_discrete"
+                self._head = (policy.n_choices, table)
             bufs = _lib.RrBuffers()
             _lib.check(self._lib.rr_get_buffers(batch._h, ctypes.byref(bufs)), "rr_get_buffers")
             self._term_obs = ctypes.c_void_p(bufs.terminal_obs)
@@ -194,7 +212,7 @@ class DeviceRollout:
     def _collect_fused(self):
         """one_launch: the whole rollout + GAE in one rr_rollout_collect launch, or (per_step)
         one rr_rollout_step per step (the env's obs buffer is written on the last step only),
-        then V(last obs). Otherwise two launches per step: rr_policy_act
+        then V(last obs); their _discrete twins for a Categorical policy. Otherwise two launches per step: rr_policy_act
         (forward + sample of step t, bootstrap of step t-1, episode-start flags) and the
         fused env step; obs are read in place from the env's output buffer."""
         env, lib, c, p = self.env, self._lib, self._c, self._p
@@ -217,22 +235,21 @@ class DeviceRollout:
             self.iter.add_(1)
             return
         if self.one_launch and not self.per_step:
-            _lib.check(lib.rr_rollout_collect(env._h, params, prec, self.seed, it, self.n_steps, self.gamma, self.lam,
-                                              p(self.obs), p(self.actions), p(self.values), p(self.log_probs),
-                                              p(self.starts), p(self.rewards), p(self.advantages), p(self.returns),
-                                              p(self.last_value), p(self.last_done), p(self.last_start), obs,
-                                              p(env.reward), done, p(env.truncated), p(env.terms), stream),
-                       "rr_rollout_collect")
+            _lib.check(getattr(lib, self._collect)(env._h, params, *self._head, prec, self.seed, it, self.n_steps,
+                                                   self.gamma, self.lam, p(self.obs), p(self.actions), p(self.values),
+                                                   p(self.log_probs), p(self.starts), p(self.rewards),
+                                                   p(self.advantages), p(self.returns), p(self.last_value),
+                                                   p(self.last_done), p(self.last_start), obs, p(env.reward), done,
+                                                   p(env.truncated), p(env.terms), stream), self._collect)
             self.iter.add_(1)
             return
         if self.one_launch:
-            T = self.n_steps
+            T, step = self.n_steps, getattr(lib, self._step)
             for t in range(T):
-                _lib.check(lib.rr_rollout_step(env._h, params, prec, self.seed, it, t, self.gamma, p(self.obs[t]),
-                                               p(self.actions[t]), p(self.values[t]), p(self.log_probs[t]),
-                                               p(self.starts[t]), p(self.rewards[t]), obs if t == T - 1 else None,
-                                               p(env.reward), done, p(env.truncated), p(env.terms), stream),
-                           "rr_rollout_step")
+                _lib.check(step(env._h, params, *self._head, prec, self.seed, it, t, self.gamma, p(self.obs[t]),
+                                p(self.actions[t]), p(self.values[t]), p(self.log_probs[t]), p(self.starts[t]),
+                                p(self.rewards[t]), obs if t == T - 1 else None, p(env.reward), done,
+                                p(env.truncated), p(env.terms), stream), self._step)
             _lib.check(lib.rr_policy_bootstrap(params, ns, na, prec, n, None, None, None, self.gamma, None, obs,
                                                p(self.last_value), stream), "rr_policy_bootstrap")
             self._finish(stream)
