@@ -769,6 +769,39 @@ int rr_ppo_update_discrete(int obs_dim, int n_choices, float* const* params, flo
                            const float* lr, double beta1, double beta2, float eps, float* stats, uint32_t flags,
                            void* workspace, int64_t workspace_bytes, void* stream);
 
+/* rr_ppo_update_opts for this policy: rr_ppo_update_discrete with SB3's clip_range_vf,
+ * normalize_advantage and target_kl, and PPO.train's early stop and logging carried on the device.
+ * Arguments are rr_ppo_update_discrete's, plus rr_ppo_update_opts's in its places: old_values [*]
+ * after returns (the rollout's values, gathered by idx; required with clip_range_vf > 0, else may be
+ * NULL), options (host) and control (device, RR_PPO_CTL_SLOTS floats, 16-B aligned, or NULL without
+ * target_kl and train_stats) ahead of stats, and the flag RR_PPO_EPOCH_START. stats may be NULL.
+ * The loss is rr_ppo_update_discrete's (log_prob = log p_a, the state-dependent entropy with its
+ * gradient in each sample's logit gradient) with rr_ppo_update_opts's three replacements: the value
+ * clip on the vf tower, raw advantages[idx] with normalize_advantage 0, and the stop at
+ * approx_kl > 1.5 target_kl. The control block is the caller's and means what it means there:
+ * RR_PPO_CTL_SUM_ENTROPY sums the minibatches' mean entropies (stats[2]), a stopping minibatch takes
+ * no optimizer step and sets RR_PPO_CTL_STOP, and with RR_PPO_CTL_STOP set every call is a no-op for
+ * parameters, optimizer state, stats, the workspace and the block itself (each kernel reads the word
+ * at entry and returns).
+ *
+ * With clip_range_vf = 0, target_kl = 0 and normalize_advantage = 1 the call computes bitwise what
+ * rr_ppo_update_discrete computes, chained or not, with or without a control block. Four launches
+ * (three chained) on `stream`, capturable in a graph; deterministic: every sum in a fixed order,
+ * every word of the block with one writer per launch. RR_EINVAL before any launch for what
+ * rr_ppo_update_discrete refuses and for: NaN or negative clip_range_vf / target_kl,
+ * clip_range_vf > 0 without old_values, target_kl > 0 or train_stats without control, a control
+ * pointer that is not 16-B aligned, unknown flag bits, NULL options.
+ * workspace: rr_ppo_update_discrete_opts_workspace_size bytes. */
+int rr_ppo_update_discrete_opts_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes);
+int rr_ppo_update_discrete_opts(int obs_dim, int n_choices, float* const* params, float* const* grads,
+                                float* const* exp_avg, float* const* exp_avg_sq, float* const* step, const float* obs,
+                                const float* actions, const float* old_log_prob, const float* advantages,
+                                const float* returns, const float* old_values, const int64_t* idx, int64_t batch,
+                                const int64_t* next_idx, int64_t next_batch, float clip_range, float ent_coef,
+                                float vf_coef, float max_grad_norm, const float* lr, double beta1, double beta2,
+                                float eps, const rr_ppo_options* options, float* control, float* stats, uint32_t flags,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+
 /* rr_bc_update for this policy: one behaviour-cloning minibatch step on demonstrations obs [M][7] and
  * actions [M], the demonstrated index as a float (what rr_policy_act_discrete writes and what the
  * reference's RecordTrajectoryCallback records behind DiscreteActions3DOF), rows idx[0 .. batch):

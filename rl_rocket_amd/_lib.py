@@ -232,6 +232,12 @@ SIGNATURES = {
                                [ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                 ctypes.c_float, _P, ctypes.c_double, ctypes.c_double, ctypes.c_float, _P,
                                 ctypes.c_uint32, _P, ctypes.c_int64, _P]),
+    "rr_ppo_update_discrete_opts_workspace_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P]),
+    "rr_ppo_update_discrete_opts": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 12 +
+                                    [ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_float, ctypes.c_float,
+                                     ctypes.c_float, ctypes.c_float, _P, ctypes.c_double, ctypes.c_double,
+                                     ctypes.c_float, ctypes.POINTER(RrPpoOptions), _P, _P, ctypes.c_uint32, _P,
+                                     ctypes.c_int64, _P]),
     "rr_bc_update_discrete_workspace_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P]),
     "rr_bc_update_discrete": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 8 +
                               [ctypes.c_int64, ctypes.c_float, ctypes.c_float, _P, ctypes.c_double, ctypes.c_double,

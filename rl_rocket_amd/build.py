@@ -54,6 +54,10 @@ SRC_BC_DISCRETE = os.path.join(HERE, "csrc", "bc_discrete", "rocket_bc_discrete.
 # rr_policy_evaluate_discrete): the collect's and the evaluation's bodies with the Categorical head, in a
 # module of their own for the same reason, with the collect's settings
 SRC_ROLLOUT_DISCRETE = os.path.join(HERE, "csrc", "rollout_discrete", "rocket_rollout_discrete.hip")
+# that policy's learner with SB3's clip_range_vf / normalize_advantage / target_kl options and the device-side
+# train() statistics (rr_ppo_update_discrete_opts): the discrete unit's learner kernels in the learner-options
+# unit's frames, in a module of their own for the same reason, with the learner's settings
+SRC_DISCRETE_OPTS = os.path.join(HERE, "csrc", "discrete_opts", "rocket_ppo_discrete_opts.hip")
 HEADER = os.path.join(ROOT, "include", "rocket_hip.h")
 OUT = os.path.join(HERE, "librocket_hip.so")
 # benchmark-only helper (not part of the product ABI): bench.py's event-timed direct-launch region
@@ -89,16 +93,16 @@ def command(resource_usage=False, out=OUT, defines=(), extra=(), src=SRC, compil
 
 
 def sources():
-    """Every file the eleven translation units are compiled from: all of csrc/ (three units and the
+    """Every file the twelve translation units are compiled from: all of csrc/ (three units and the
     text the others include, the behaviour-cloning kernels' rocket_bc.inc among it), the recording and
     the exact-mode evaluation's units, the statistics collect's unit with the .inc beside it, the
-    learner-options, behaviour-cloning, discrete-action, discrete behaviour-cloning and discrete-rollout units
-    and the C-ABI header, sorted (tests/test_build_sources.py checks that the #include graph stays inside this
-    list)."""
+    learner-options, behaviour-cloning, discrete-action, discrete behaviour-cloning, discrete-rollout and
+    discrete learner-options units and the C-ABI header, sorted (tests/test_build_sources.py checks that the
+    #include graph stays inside this list)."""
     csrc = os.path.join(HERE, "csrc")
     return sorted([os.path.join(csrc, f) for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))]
                   + [SRC_EVAL_TRACE, SRC_EVAL_EXACT, SRC_COLLECT_STATS, INC_COLLECT_STATS, SRC_PPO_OPTS, SRC_BC, SRC_DISCRETE,
-                     SRC_BC_DISCRETE, SRC_ROLLOUT_DISCRETE, HEADER])
+                     SRC_BC_DISCRETE, SRC_ROLLOUT_DISCRETE, SRC_DISCRETE_OPTS, HEADER])
 
 
 def source_hash():
@@ -117,11 +121,11 @@ def source_hash():
 
 
 def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
-    """The six hipcc calls that build the library's eleven translation units: the main, exact-mode,
+    """The six hipcc calls that build the library's twelve translation units: the main, exact-mode,
     collect, recording-evaluation and exact-evaluation units compiled to objects (the latter four with EXACT_FLAGS /
     COLLECT_FLAGS / COLLECT_FLAGS / EVAL_EXACT_FLAGS); the last step compiles the learner-options, the
-    behaviour-cloning, the discrete-action, the discrete behaviour-cloning, the discrete-rollout and the
-    statistics collect's units
+    behaviour-cloning, the discrete-action, the discrete behaviour-cloning, the discrete-rollout, the discrete
+    learner-options and the statistics collect's units
     (all COLLECT_FLAGS, each a module of its own) and links them with
     those objects into `out` in one hipcc call. The flags of that call reach only the sources it
     compiles: the objects already hold their code objects."""
@@ -138,14 +142,14 @@ def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
                  preload=preload)
     objs = [o_main, o_exact, o_coll, o_trace, o_evx]
     c6 = command(resource_usage, out, defines, list(extra) + COLLECT_FLAGS + objs + [SRC_PPO_OPTS, SRC_BC, SRC_DISCRETE, SRC_BC_DISCRETE,
-                                                                            SRC_ROLLOUT_DISCRETE],
+                                                                            SRC_ROLLOUT_DISCRETE, SRC_DISCRETE_OPTS],
                  SRC_COLLECT_STATS,
                  preload=preload)
     return [c1, c2, c3, c4, c5, c6]
 
 
 def build_lib(out=OUT, defines=(), extra=(), resource_usage=False, verbose=True, preload=4):
-    """Compile five translation units to objects (in parallel), then the other six in the call that
+    """Compile five translation units to objects (in parallel), then the other seven in the call that
     links `out`."""
     cmds = commands(resource_usage, out, defines, extra, preload=preload)
     if verbose:

@@ -1234,4 +1234,6 @@ __attribute__((visibility("hidden"))) int rrc_launch_bc_discrete(const void* lau
 __attribute__((visibility("hidden"))) int rrc_launch_rollout_discrete(const void* launch, const void* io, const void* head,
                                                                       int multi);
 __attribute__((visibility("hidden"))) int rrc_launch_eval_discrete(const void* launch, const void* io, const void* head);
+// discrete_opts/rocket_ppo_discrete_opts.hip: rr_ppo_update_discrete_opts's launches, a DiscreteOptsLaunch
+__attribute__((visibility("hidden"))) int rrc_launch_discrete_opts(const void* launch, void* stream);
 }

@@ -384,6 +384,7 @@ __attribute__((weak)) int rrc_launch_discrete(const void*, void*) { return kNoUn
 __attribute__((weak)) int rrc_launch_bc_discrete(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_rollout_discrete(const void*, const void*, const void*, int) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval_discrete(const void*, const void*, const void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_discrete_opts(const void*, void*) { return kNoUnit; }
 }
 
 namespace {
@@ -1934,6 +1935,27 @@ int ppo_update_record(const char* who, PpoLaunch& L, const LearnerShape& sh, flo
     L.flags = flags & RR_PPO_CHAINED;
     return RR_OK;
 }
+
+// The option checks of rr_ppo_update_opts and rr_ppo_update_discrete_opts and the options' fields of their
+// launch records (a generic lambda: no template inside extern "C")
+const auto ppo_options_record = [](const char* who, auto& O, const rr_ppo_options* options, const float* old_values,
+                                   float* control, uint32_t flags) {
+    if (!options) return refuse(who, "null options");
+    // NaN fails both comparisons' complements: !(x >= 0) is true for NaN and for negatives
+    if (!(options->clip_range_vf >= 0.0f)) return refuse(who, "clip_range_vf must be >= 0 (0: off)");
+    if (!(options->target_kl >= 0.0f)) return refuse(who, "target_kl must be >= 0 (0: off)");
+    if (options->clip_range_vf > 0.0f && !old_values) return refuse(who, "clip_range_vf needs old_values");
+    if (options->target_kl > 0.0f && !control) return refuse(who, "target_kl needs a control block");
+    if (options->train_stats && !control) return refuse(who, "train_stats needs a control block");
+    if (((uintptr_t)control & 15) != 0) return refuse(who, "control block must be 16-B aligned");
+    O.old_values = old_values;
+    O.clip_vf = options->clip_range_vf;
+    O.normalize = options->normalize_advantage != 0;
+    O.ctl.ctl = control;
+    O.ctl.kl_limit = options->target_kl > 0.0f ? 1.5f * options->target_kl : HUGE_VALF;
+    O.ctl.epoch_start = (flags & RR_PPO_EPOCH_START) != 0;
+    return (int)RR_OK;
+};
 }  // namespace
 
 int rr_ppo_update(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* exp_avg,
@@ -1990,22 +2012,8 @@ int rr_ppo_update_opts(int obs_dim, int act_dim, float* const* params, float* co
                                      clip_range, ent_coef, vf_coef, max_grad_norm, lr, beta1, beta2, eps, stats, flags,
                                      RR_PPO_CHAINED | RR_PPO_EPOCH_START, workspace, workspace_bytes, need);
     if (rc != RR_OK) return rc;
-    if (!options) return fail(RR_EINVAL, "rr_ppo_update_opts: null options");
-    // NaN fails both comparisons' complements: !(x >= 0) is true for NaN and for negatives
-    if (!(options->clip_range_vf >= 0.0f)) return fail(RR_EINVAL, "rr_ppo_update_opts: clip_range_vf must be >= 0 (0: off)");
-    if (!(options->target_kl >= 0.0f)) return fail(RR_EINVAL, "rr_ppo_update_opts: target_kl must be >= 0 (0: off)");
-    if (options->clip_range_vf > 0.0f && !old_values)
-        return fail(RR_EINVAL, "rr_ppo_update_opts: clip_range_vf needs old_values");
-    if (options->target_kl > 0.0f && !control) return fail(RR_EINVAL, "rr_ppo_update_opts: target_kl needs a control block");
-    if (options->train_stats && !control)
-        return fail(RR_EINVAL, "rr_ppo_update_opts: train_stats needs a control block");
-    if (((uintptr_t)control & 15) != 0) return fail(RR_EINVAL, "rr_ppo_update_opts: control block must be 16-B aligned");
-    O.old_values = old_values;
-    O.clip_vf = options->clip_range_vf;
-    O.normalize = options->normalize_advantage != 0;
-    O.ctl.ctl = control;
-    O.ctl.kl_limit = options->target_kl > 0.0f ? 1.5f * options->target_kl : HUGE_VALF;
-    O.ctl.epoch_start = (flags & RR_PPO_EPOCH_START) != 0;
+    if (const int rc2 = ppo_options_record("rr_ppo_update_opts", O, options, old_values, control, flags); rc2 != RR_OK)
+        return rc2;
     if (!stats) O.base.stats = (float*)((char*)workspace + ppo_update_bytes(sh, batch));
     const hipError_t err = (hipError_t)rrc_launch_learner_opts(&O, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_opts: launch");
@@ -2287,6 +2295,47 @@ int rr_ppo_update_discrete(int obs_dim, int n_choices, float* const* params, flo
     D.u.pg.p[12] = D.sink + 64 * 4 + 4;
     const hipError_t err = (hipError_t)rrc_launch_discrete(&D, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_discrete: launch");
+}
+
+int rr_ppo_update_discrete_opts_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes)
+{
+    const int rc = disc_learner_ok("rr_ppo_update_discrete_opts_workspace_size", obs_dim, n_choices, batch, bytes);
+    // rr_ppo_update_discrete's sections, + 8 floats: the call's statistics when the caller passes none
+    if (rc == RR_OK) *bytes = ppo_update_bytes(disc_shape(n_choices), batch) + kDiscSink * (int64_t)sizeof(float) + 32;
+    return rc;
+}
+
+int rr_ppo_update_discrete_opts(int obs_dim, int n_choices, float* const* params, float* const* grads,
+                                float* const* exp_avg, float* const* exp_avg_sq, float* const* step, const float* obs,
+                                const float* actions, const float* old_log_prob, const float* advantages,
+                                const float* returns, const float* old_values, const int64_t* idx, int64_t batch,
+                                const int64_t* next_idx, int64_t next_batch, float clip_range, float ent_coef,
+                                float vf_coef, float max_grad_norm, const float* lr, double beta1, double beta2,
+                                float eps, const rr_ppo_options* options, float* control, float* stats, uint32_t flags,
+                                void* workspace, int64_t workspace_bytes, void* stream)
+{
+    const char* who = "rr_ppo_update_discrete_opts";
+    if (const int rc = disc_learner_ok(who, obs_dim, n_choices, batch, nullptr, false); rc != RR_OK) return rc;
+    const LearnerShape sh = disc_shape(n_choices);
+    const int64_t sink_at = ppo_update_bytes(sh, batch);
+    const int64_t stats_at = sink_at + kDiscSink * (int64_t)sizeof(float);
+    DiscreteOptsLaunch O = {};
+    DiscreteLaunch& D = O.base;
+    PpoLaunch u;  // ppo_update_record assigns the whole record
+    const int rc = ppo_update_record(who, u, sh, params, grads, exp_avg, exp_avg_sq, step, obs, actions, old_log_prob,
+                                     advantages, returns, idx, batch, next_idx, next_batch, clip_range, ent_coef, vf_coef,
+                                     max_grad_norm, lr, beta1, beta2, eps, stats, flags,
+                                     RR_PPO_CHAINED | RR_PPO_EPOCH_START, workspace, workspace_bytes, stats_at + 32);
+    if (rc != RR_OK) return rc;
+    if (const int rc2 = ppo_options_record(who, O, options, old_values, control, flags); rc2 != RR_OK) return rc2;
+    D.op = kDiscUpdate;
+    D.n_choices = n_choices;
+    D.u = u;
+    D.sink = (float*)((char*)workspace + sink_at);
+    D.u.pg.p[12] = D.sink + 64 * 4 + 4;
+    if (!stats) D.u.stats = (float*)((char*)workspace + stats_at);
+    const hipError_t err = (hipError_t)rrc_launch_discrete_opts(&O, stream);
+    return err == hipSuccess ? RR_OK : hip_fail(err, "rr_ppo_update_discrete_opts: launch");
 }
 
 int rr_bc_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes)

@@ -927,6 +927,18 @@ struct DiscreteLaunch {
 };
 static_assert(std::is_trivially_copyable_v<DiscreteLaunch>, "DiscreteLaunch crosses TUs by memcpy");
 
+// rr_ppo_update_discrete_opts's launches (discrete_opts/rocket_ppo_discrete_opts.hip,
+// rrc_launch_discrete_opts): an rr_ppo_update_discrete launch record (kDiscUpdate) and the options,
+// as PpoOptsLaunch extends PpoLaunch; base.u.stats is never null (the caller's, or workspace floats)
+struct DiscreteOptsLaunch {
+    DiscreteLaunch base;
+    const float* old_values;  // the value clip's rollout values (clip_vf > 0)
+    float clip_vf;            // <= 0: off
+    int normalize;            // normalize_advantage
+    ppo::CtlArgs ctl;
+};
+static_assert(std::is_trivially_copyable_v<DiscreteOptsLaunch>, "DiscreteOptsLaunch crosses TUs by memcpy");
+
 // Element k of policy tensor t (rr_ppo_grad order) into the packed images (two towers of Pack::SIZE).
 template <int OBS, int ACT>
 __device__ __forceinline__ void pack_scatter(float* __restrict__ pack, int t, int k, float v)

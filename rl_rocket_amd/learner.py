@@ -4,10 +4,11 @@
 captured into a hipGraph (``GraphedPPOUpdate``). ``_AdamState`` is the binding of the 13 policy
 tensors and a capturable Adam's state that the fused calls share with ``bc.BCUpdate``.
 ``PPOUpdate`` serves both distributions: for a ``MlpCategoricalActorCritic`` its constructor chooses
-``rr_ppo_update_discrete``, ``(ns, n_choices)`` as the shape, the actions as ``[n]`` indices and the
-policy's 12 tensors, and refuses the options; ``__call__`` is the same. ``PPOUpdateDiscrete`` is that
-path under its own name. ``ppo_update`` and ``GraphedPPOUpdate`` share their refusals
-(``_refuse_options``) and build the whole-minibatch step through ``_whole_step``.
+``rr_ppo_update_discrete`` (``rr_ppo_update_discrete_opts`` with an option or ``train_stats``),
+``(ns, n_choices)`` as the shape, the actions as ``[n]`` indices and the policy's 12 tensors;
+``__call__`` is the same. ``PPOUpdateDiscrete`` is that path under its own name. ``ppo_update`` and
+``GraphedPPOUpdate`` share their refusals (``_refuse_options``) and build the whole-minibatch step
+through ``_whole_step``.
 """
 import ctypes
 
@@ -247,16 +248,21 @@ def _train_stats(ctl):
             "train/stop_epoch": int(ctl[L.RR_PPO_CTL_EPOCHS]) - 1 if stopped else None}
 
 
-_DISCRETE_FUSED = ("the fused Categorical learner (rr_ppo_update_discrete) is the one-replica call with a capturable "
-                   "torch.optim.Adam and SB3's defaults: %s needs fused=False (the autograd path takes it)")
+_DISCRETE_FUSED = ("the fused Categorical learner (rr_ppo_update_discrete, rr_ppo_update_discrete_opts) is the "
+                   "one-replica call with a capturable torch.optim.Adam: %s needs fused=False (the autograd path "
+                   "takes it)")
 
 
-def _discrete_fused_ok(group, cvf, norm, tkl, train_stats=False):
-    """Refuses the arguments ``fused=True`` does not take for a Categorical policy, before any device work."""
-    what = ("group=" if group is not None else "clip_range_vf" if cvf else "normalize_advantage=False" if not norm
-            else "target_kl" if tkl else "train_stats" if train_stats else None)
-    if what:
-        raise ValueError(_DISCRETE_FUSED % what)
+def _discrete_fused_ok(group, one_call, cvf, norm, tkl, train_stats=False):
+    """Refuses what ``fused=True`` does not take for a Categorical policy, before any device work: a
+    ``group``, and an optimizer that is no capturable CUDA Adam over the policy's parameters (named by
+    the option that asked for the fused call, if there is one)."""
+    if group is not None:
+        raise ValueError(_DISCRETE_FUSED % "group=")
+    if not one_call:
+        what = ("clip_range_vf" if cvf else "normalize_advantage=False" if not norm else "target_kl" if tkl
+                else "train_stats" if train_stats else None)
+        raise ValueError(_DISCRETE_FUSED % ("%s with another optimizer" % what if what else "another optimizer"))
 
 
 class PPOUpdate(PPOGrad, _AdamState):
@@ -276,7 +282,8 @@ class PPOUpdate(PPOGrad, _AdamState):
 
     SB3's ``clip_range_vf``, ``normalize_advantage=False`` and ``target_kl`` (None / True / None:
     today's ``rr_ppo_update`` calls, unchanged), or ``train_stats=True``, take the same step through
-    ``rr_ppo_update_opts``. That call carries a control block on the device (``self.ctl``):
+    ``rr_ppo_update_opts`` (``rr_ppo_update_discrete_opts`` for a Categorical policy). That call
+    carries a control block on the device (``self.ctl``):
       * ``reset()`` clears it; call it before the first minibatch of a ``train()``-like pass and pass
         ``epoch_start=True`` with every epoch's first minibatch.
       * With ``target_kl``, the minibatch whose ``approx_kl > 1.5 target_kl`` takes no optimizer
@@ -297,13 +304,12 @@ class PPOUpdate(PPOGrad, _AdamState):
             raise ValueError("%s needs a capturable torch.optim.Adam over the policy's parameters "
                              "(one group, no weight decay / amsgrad / maximize)" % who)
         if self._categorical or isinstance(policy, MlpCategoricalActorCritic):
-            # what differs: the call, (ns, n_choices) as its shape, the actions as [n] indices, no options
+            # what differs: the calls, (ns, n_choices) as their shape, the actions as [n] indices
             ns = ro.env.state_dim
             if not fused_discrete_supported(policy, ns):
                 raise ValueError("%s needs an MlpCategoricalActorCritic with 64x64 towers and 2 .. 4 "
                                  "choices on a 3DOF rollout" % who)
-            _discrete_fused_ok(None, cvf, norm, tkl, train_stats)
-            self._call = "rr_ppo_update_discrete"
+            self._call = "rr_ppo_update_discrete" if self.opts is None else "rr_ppo_update_discrete_opts"
             dev = self._bind_rollout(self._call, policy, ro, batch_size, (ns, policy.n_choices), (), clip_range,
                                      ent_coef, vf_coef)
         else:
@@ -320,7 +326,7 @@ class PPOUpdate(PPOGrad, _AdamState):
             if cvf:
                 self.old_values = _old_values(ro, self.data[0].shape[0])
         # the call's leading arguments, the same every time: the shape, the five pointer arrays, the rollout
-        # (rr_ppo_update_opts: old_values after it)
+        # (rr_ppo_update_opts, rr_ppo_update_discrete_opts: old_values after it)
         self._head = [self.ns, self.na, *self._ptrs, *[t.data_ptr() for t in self.data]]
         if self.opts is not None:
             self._head.append(None if self.old_values is None else self.old_values.data_ptr())
@@ -363,22 +369,24 @@ class PPOUpdateDiscrete(PPOUpdate):
     constructor it had as a class of its own: one PPO minibatch step with a Categorical distribution as
     ONE library call (``rr_ppo_update_discrete``: the learner's towers with a softmax head, the
     entropy's gradient per sample, clip + Adam over the policy's 12 tensors). ``stats[2]`` is the
-    minibatch's mean entropy. SB3's defaults only: no ``clip_range_vf``, ``target_kl``, raw advantages
-    or control block (``opts`` is None)."""
+    minibatch's mean entropy. ``clip_range_vf``, ``normalize_advantage=False``, ``target_kl`` and
+    ``train_stats=True`` are ``PPOUpdate``'s (``rr_ppo_update_discrete_opts``, with the control block,
+    ``reset()``, ``train_stats()`` and ``epoch_start=``); without them ``opts`` is None and the call is
+    ``rr_ppo_update_discrete``."""
 
     _categorical = True
 
     def __init__(self, policy, optimizer, ro, batch_size, clip_range=0.2, ent_coef=0.01, vf_coef=0.5,
-                 max_grad_norm=0.5):
-        super().__init__(policy, optimizer, ro, batch_size, clip_range, ent_coef, vf_coef, max_grad_norm)
+                 max_grad_norm=0.5, clip_range_vf=None, normalize_advantage=True, target_kl=None, train_stats=False):
+        super().__init__(policy, optimizer, ro, batch_size, clip_range, ent_coef, vf_coef, max_grad_norm,
+                         clip_range_vf, normalize_advantage, target_kl, train_stats)
 
 
 def _whole_step(policy, optimizer, ro, batch_size, *coef_and_options):
     """The chained whole-minibatch call of the one-replica path (clip_range, ent_coef, vf_coef,
-    max_grad_norm, then ``PPOUpdate``'s options): ``PPOUpdateDiscrete`` for a Categorical policy,
-    whose options ``_refuse_options`` has refused by then."""
+    max_grad_norm, then ``PPOUpdate``'s options): ``PPOUpdateDiscrete`` for a Categorical policy."""
     if isinstance(policy, MlpCategoricalActorCritic):
-        return PPOUpdateDiscrete(policy, optimizer, ro, batch_size, *coef_and_options[:4])
+        return PPOUpdateDiscrete(policy, optimizer, ro, batch_size, *coef_and_options)
     return PPOUpdate(policy, optimizer, ro, batch_size, *coef_and_options)
 
 
@@ -387,9 +395,7 @@ def _refuse_options(policy, optimizer, group, fused, cvf, norm, tkl, train_stats
     whether the step is the one-call path: fused, one replica, a capturable Adam."""
     one_call = bool(fused) and group is None and clip_adam_supported(optimizer, list(policy.parameters()))
     if fused and isinstance(policy, MlpCategoricalActorCritic):
-        _discrete_fused_ok(group, cvf, norm, tkl, train_stats)
-        if not one_call:
-            raise ValueError(_DISCRETE_FUSED % "another optimizer")
+        _discrete_fused_ok(group, one_call, cvf, norm, tkl, train_stats)
     if tkl and group is not None:
         raise ValueError("target_kl with a group is not supported: the ranks would stop at different minibatches")
     if graphed and not one_call and (train_stats or tkl or (fused and (cvf or not norm))):
@@ -480,7 +486,8 @@ def ppo_update(policy, optimizer, ro, n_epochs=10, batch_size=65536, clip_range=
     A ``MlpCategoricalActorCritic`` (discrete 3DOF actions): the autograd path takes everything above,
     with the entropy from the logits. ``fused=True`` is ``PPOUpdateDiscrete``
     (``rr_ppo_update_discrete``, chained) and needs a capturable Adam and no ``group``;
-    ``clip_range_vf``, ``normalize_advantage=False`` and ``target_kl`` raise there."""
+    ``clip_range_vf``, ``normalize_advantage=False`` and ``target_kl`` put it on
+    ``rr_ppo_update_discrete_opts``, the stop carried on the device as for the Gaussian policy."""
     n = ro.n_steps * ro.env.num_envs
     cvf, norm, tkl = _ppo_options(clip_range_vf, normalize_advantage, target_kl)
     one_call = _refuse_options(policy, optimizer, group, fused, cvf, norm, tkl)
@@ -575,7 +582,8 @@ class GraphedPPOUpdate:
 
     ``clip_range_vf`` / ``normalize_advantage`` / ``target_kl`` / ``train_stats`` (SB3's defaults and
     False: exactly the calls described above) put the fused one-replica path on
-    ``rr_ppo_update_opts`` (``PPOUpdate``). ``update`` then clears the control block, every epoch's
+    ``rr_ppo_update_opts`` (``PPOUpdate``; ``rr_ppo_update_discrete_opts`` for a Categorical policy).
+    ``update`` then clears the control block, every epoch's
     first minibatch is captured with the epoch-start flag, and a KL stop needs no host decision: the
     epochs after it replay as no-ops, and ``update`` still never waits for the device on their
     account. ``train_stats()`` returns SB3's ``train/*`` means over the last ``update`` with one
@@ -583,8 +591,10 @@ class GraphedPPOUpdate:
     refuses ``target_kl`` (a ``break`` cannot be captured); the split multi-GPU path refuses all.
 
     A ``MlpCategoricalActorCritic``: ``fused`` defaults to True where ``PPOUpdateDiscrete`` applies
-    (one replica, capturable Adam, SB3's defaults) and captures its chained calls; the options and
-    ``group`` raise with ``fused=True`` and are captured as PyTorch ops with ``fused=False``."""
+    (one replica, capturable Adam, SB3's defaults) and captures its chained calls. An option or
+    ``train_stats`` keeps that default off the fused path; ``fused=True`` takes them
+    (``rr_ppo_update_discrete_opts``: the control block, the KL stop and ``train_stats()`` as above).
+    ``group`` raises with ``fused=True`` and is captured as PyTorch ops with ``fused=False``."""
 
     def __init__(self, policy, optimizer, ro, batch_size=65536, clip_range=0.2, ent_coef=0.01, vf_coef=0.5,
                  max_grad_norm=0.5, group=None, fused=None, clip_range_vf=None, normalize_advantage=True,
