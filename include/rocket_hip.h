@@ -871,6 +871,40 @@ int rr_rollout_collect_discrete(rr_env* e, const float* params, int n_choices, c
 int rr_policy_evaluate_discrete(rr_env* e, const float* params, int n_choices, const float* table, int precision,
                                 int n_episodes, int64_t max_steps, const rr_eval_out* out, float* obs, void* stream);
 
+/* The same two one-launch calls with the collect statistics and with recorded episodes (pure additions
+ * to ABI 14). Handle, params, n_choices, table and precision are as above.
+ *
+ * rr_rollout_collect_discrete_stats is rr_rollout_collect_discrete that also fills `stats` as
+ * rr_rollout_collect_stats does: the same slots, the same rows of partials (rr_rollout_stats_rows), the
+ * same fixed-order reduction launched after it on the same stream, `accum` folded when given. The
+ * rollout buffers, env outputs and the handle's state are bitwise rr_rollout_collect_discrete's
+ * (tests/test_gpu_collect_stats_discrete.py). RR_EINVAL before any HIP call for what
+ * rr_rollout_collect_discrete refuses and for what rr_rollout_collect_stats refuses: stats,
+ * stats->partials or stats->out NULL, partials not 128-B aligned, out / accum not 8-B aligned,
+ * buf_advantage or buf_return NULL, a handle without RR_FLAG_EPISODE_STATS or RR_FLAG_AUTO_RESET. The
+ * argument checks come before the handle is read.
+ *
+ * rr_policy_evaluate_discrete_trace is rr_policy_evaluate_discrete that also records the envs with a
+ * trace slot as rr_policy_evaluate_trace does (rr_eval_trace is unchanged: state rows, action rows,
+ * terms, length; the recorded action row is the table row the env stepped with). choice, device memory
+ * [n_slots][n_episodes][steps] int32 or NULL, receives the index of that row, k in [0, n_choices),
+ * written where the action row is written (t < steps; rows past an episode's length are not touched).
+ * Outputs, the state left and obs are bitwise rr_policy_evaluate_discrete's
+ * (tests/test_gpu_eval_trace_discrete.py). RR_EINVAL before any HIP call for what
+ * rr_policy_evaluate_discrete refuses and for what rr_policy_evaluate_trace refuses: trace,
+ * trace->slot, trace->state or trace->length NULL, trace->n_slots or trace->steps below 1; and for a
+ * choice that is not 4-B aligned. */
+int rr_rollout_collect_discrete_stats(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                                      uint64_t seed, const uint64_t* iter, int n_steps, double gamma,
+                                      double gae_lambda, float* buf_obs, float* buf_action, float* buf_value,
+                                      float* buf_log_prob, float* buf_start, float* buf_reward, float* buf_advantage,
+                                      float* buf_return, float* last_value, float* last_done, float* last_start,
+                                      float* obs, float* reward, uint8_t* done, uint8_t* truncated, float* terms,
+                                      const rr_rollout_stats* stats, void* stream);
+int rr_policy_evaluate_discrete_trace(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                                      int n_episodes, int64_t max_steps, const rr_eval_out* out,
+                                      const rr_eval_trace* trace, int32_t* choice, float* obs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

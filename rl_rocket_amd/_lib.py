@@ -249,6 +249,14 @@ SIGNATURES = {
                                                    ctypes.c_int, ctypes.c_double, ctypes.c_double] + [_P] * 17),
     "rr_policy_evaluate_discrete": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int,
                                                    ctypes.c_int64, ctypes.POINTER(RrEvalOut), _P, _P]),
+    # rr_rollout_collect_stats's / rr_policy_evaluate_trace's arguments with (n_choices, table) after params;
+    # the latter with the choice plane after the trace
+    "rr_rollout_collect_discrete_stats": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_uint64, _P,
+                                                         ctypes.c_int, ctypes.c_double, ctypes.c_double] + [_P] * 16 +
+                                          [ctypes.POINTER(RrRolloutStats), _P]),
+    "rr_policy_evaluate_discrete_trace": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int,
+                                                         ctypes.c_int64, ctypes.POINTER(RrEvalOut),
+                                                         ctypes.POINTER(RrEvalTrace), _P, _P, _P]),
 }
 
 _LIB = None

@@ -92,7 +92,9 @@ class Demonstrations:
         ``t < length``: ``obs`` is the recorded state row ``t`` times the float32 reciprocal
         normaliser of ``batch`` (``float32(1 / state_normalizer)``, what the handle's kernels
         multiply by), so on an RK4 / Euler batch it is bitwise the observation the policy was given;
-        ``acts`` is the recorded action, the clipped mean the env stepped with.
+        ``acts`` is the recorded action, the clipped mean the env stepped with. A trace with a ``choice``
+        plane (a Categorical policy's) gives ``acts`` [M, 1], the chosen indices as floats: what ``BCUpdate``
+        and ``bc_train`` take for an ``MlpCategoricalActorCritic``.
 
         Row order: slot-major (the order of ``record=``), then episode, then step. Episodes cut by
         ``max_steps`` (partial) and episodes longer than the recording capacity (clipped) are left
@@ -111,6 +113,8 @@ class Demonstrations:
         inv = torch.tensor((1.0 / np.asarray(batch.cfg.state_normalizer, dtype=np.float64)).astype(np.float32),
                            device=dev)[:trace.state.shape[-1]]
         obs = trace.state[:, :, :cap][mask] * inv
+        if getattr(trace, "choice", None) is not None:
+            return cls(obs.contiguous(), trace.choice[mask].to(torch.float32).reshape(-1, 1).contiguous())
         return cls(obs.contiguous(), trace.action[mask].contiguous())
 
 

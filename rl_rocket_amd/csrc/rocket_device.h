@@ -1234,6 +1234,14 @@ __attribute__((visibility("hidden"))) int rrc_launch_bc_discrete(const void* lau
 __attribute__((visibility("hidden"))) int rrc_launch_rollout_discrete(const void* launch, const void* io, const void* head,
                                                                       int multi);
 __attribute__((visibility("hidden"))) int rrc_launch_eval_discrete(const void* launch, const void* io, const void* head);
+// collect_stats_discrete/rocket_collect_stats_discrete.hip: the Categorical policy's one-launch collect with the
+// episode statistics and their reduction; head / stats point to the caller's DiscHead / CollectStatsIO
+__attribute__((visibility("hidden"))) int rrc_launch_collect_discrete_stats(const void* launch, const void* io,
+                                                                            const void* head, const void* stats);
+// eval_trace_discrete/rocket_eval_trace_discrete.hip: the Categorical policy's recording one-launch evaluation;
+// trace points to the caller's EvalTraceIO, choice is the device plane of the winning indices or nullptr
+__attribute__((visibility("hidden"))) int rrc_launch_eval_discrete_trace(const void* launch, const void* io,
+                                                                         const void* head, const void* trace, void* choice);
 // discrete_opts/rocket_ppo_discrete_opts.hip: rr_ppo_update_discrete_opts's launches, a DiscreteOptsLaunch
 __attribute__((visibility("hidden"))) int rrc_launch_discrete_opts(const void* launch, void* stream);
 }

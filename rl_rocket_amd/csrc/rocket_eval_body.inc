@@ -15,6 +15,10 @@
 // MODEL 3 and PREC 0 and adds the arguments n_choices and tab, a DiscTable) selects the Categorical
 // head: the pi tower's NH = 4 heads are logits and the action is the table row of the largest of the
 // first n_choices. Not defined: the Gaussian head's clipped means.
+// Both (eval_trace_discrete/rocket_eval_trace_discrete.hip: eval_discrete_trace_kernel, which adds the argument
+// choice, an int32 plane [n_slots][n_episodes][steps] or nullptr) select one more region, seen by no other
+// kernel: the head keeps the winner's index and the step's record stores it beside the action row, under
+// the action row's t < steps rule. tr0 must stay the argument after io (trace_args reads it at that offset).
     constexpr int NS = Dims<MODEL>::NS, NA = Dims<MODEL>::NA, NT = Dims<MODEL>::NT, EV = Dims<MODEL>::EV;
     constexpr int EPW = rol::Shape<2>::kEPW, NWV = rol::Shape<2>::kWaves;
 #ifdef RR_DISCRETE_HEAD
@@ -109,12 +113,18 @@
         float zb = mean[0];
         a_env[0] = tab.v[0][0];
         a_env[1] = tab.v[0][1];
+#if RR_EVAL_TRACE
+        int32_t ci = 0;  // the winner's index, for the trace's choice plane
+#endif
 #pragma unroll
         for (int q = 1; q < NH; ++q)
             if (q < n_choices && mean[q] > zb) {
                 zb = mean[q];
                 a_env[0] = tab.v[q][0];
                 a_env[1] = tab.v[q][1];
+#if RR_EVAL_TRACE
+                ci = q;
+#endif
             }
 #else
 #pragma unroll
@@ -149,6 +159,9 @@
                     trace_row<NS>(tr.state + (e * (cap + 1u) + t + 1u) * NS, y1);
                     const uint64_t row = e * cap + t;
                     if (tr.action) trace_row<NA>(tr.action + row * NA, a_env);
+#ifdef RR_DISCRETE_HEAD
+                    if (choice) choice[row] = ci;  // the index whose table row that is
+#endif
                     if (tr.terms) {
                         gfloat_t* tp = tr.terms + row * (NT + 1);
                         trace_row<NT>(tp, tt);

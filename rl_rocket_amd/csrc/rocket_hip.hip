@@ -385,6 +385,8 @@ __attribute__((weak)) int rrc_launch_bc_discrete(const void*, void*) { return kN
 __attribute__((weak)) int rrc_launch_rollout_discrete(const void*, const void*, const void*, int) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval_discrete(const void*, const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_discrete_opts(const void*, void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_collect_discrete_stats(const void*, const void*, const void*, const void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_eval_discrete_trace(const void*, const void*, const void*, const void*, void*) { return kNoUnit; }
 }
 
 namespace {
@@ -1454,7 +1456,9 @@ int launch_rollout(rr_env* e, const char* who, bool multi, const float* params, 
     // The collect kernel (MULTI) lives in the third translation unit (rocket_collect.hip), compiled
     // with the MFMA accumulators in VGPRs (rl_rocket_amd/build.py COLLECT_FLAGS).
     hipError_t err = hipSuccess;
-    if (head) {  // the Categorical head (rollout_discrete/rocket_rollout_discrete.hip): the collect or one step
+    if (head && stats) {  // rr_rollout_collect_discrete_stats (collect_stats_discrete/): two launches
+        err = (hipError_t)rrc_launch_collect_discrete_stats(&L, &io, head, stats);
+    } else if (head) {  // the Categorical head (rollout_discrete/rocket_rollout_discrete.hip): the collect or one step
         err = (hipError_t)rrc_launch_rollout_discrete(&L, &io, head, multi);
     } else if (multi && stats) {  // rr_rollout_collect_stats (collect_stats/rocket_collect_stats.hip): two launches
         err = (hipError_t)rrc_launch_collect_stats(&L, &io, stats);
@@ -1578,10 +1582,11 @@ namespace {
 
 // rr_policy_evaluate (trace == nullptr), rr_policy_evaluate_trace and rr_policy_evaluate_exact (`exact`:
 // the handle must be an RR_INT_DOPRI5 one, where the other two refuse it): the argument checks, the
-// kernel's EvalIO and the launch. `who` prefixes every message.
+// kernel's EvalIO and the launch. `who` prefixes every message. `head`: the Categorical policy's calls
+// (rr_policy_evaluate_discrete and, traced, rr_policy_evaluate_discrete_trace with its `choice` plane).
 int evaluate(rr_env* e, const char* who, const float* params, int precision, int n_episodes, int64_t max_steps,
              const rr_eval_out* out, bool traced, const rr_eval_trace* trace, float* obs, void* stream,
-             bool exact = false, const DiscHead* head = nullptr)
+             bool exact = false, const DiscHead* head = nullptr, int32_t* choice = nullptr)
 {
     const std::string w = std::string(who) + ": ";
     if (!e) return fail(RR_EINVAL, w + "null handle");
@@ -1625,14 +1630,8 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
     // the fast modes' kernels are compiled in the collect translation units (rocket_collect.hip,
     // eval_trace/), as the collect kernel they derive from
     hipError_t err;
-    if (head) {  // rr_policy_evaluate_discrete (rollout_discrete/rocket_rollout_discrete.hip)
-        err = (hipError_t)rrc_launch_eval_discrete(&L, &io, head);
-    } else if (exact) {
-        // eval_exact_kernel (eval_exact/rocket_eval_exact.hip): eval_kernel's grid, one variant for every N
-        const EvalExactLaunch X = {e->p.model, prec, L.grid, e->d_xp, &b, e->state64, stream};
-        err = (hipError_t)rrx_launch_eval_exact(&X, &io);
-    } else if (traced) {
-        EvalTraceIO t = {};
+    EvalTraceIO t = {};
+    if (traced) {
         t.slot = trace->slot;
         t.state = trace->state;
         t.action = trace->action;
@@ -1640,6 +1639,16 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
         t.length = trace->length;
         t.n_slots = trace->n_slots;
         t.steps = trace->steps;
+    }
+    if (head && traced) {  // rr_policy_evaluate_discrete_trace (eval_trace_discrete/)
+        err = (hipError_t)rrc_launch_eval_discrete_trace(&L, &io, head, &t, choice);
+    } else if (head) {  // rr_policy_evaluate_discrete (rollout_discrete/rocket_rollout_discrete.hip)
+        err = (hipError_t)rrc_launch_eval_discrete(&L, &io, head);
+    } else if (exact) {
+        // eval_exact_kernel (eval_exact/rocket_eval_exact.hip): eval_kernel's grid, one variant for every N
+        const EvalExactLaunch X = {e->p.model, prec, L.grid, e->d_xp, &b, e->state64, stream};
+        err = (hipError_t)rrx_launch_eval_exact(&X, &io);
+    } else if (traced) {
         err = (hipError_t)rrc_launch_eval_trace(&L, &io, &t);
     } else {
         err = (hipError_t)rrc_launch_eval(&L, &io);
@@ -2261,6 +2270,59 @@ int rr_policy_evaluate_discrete(rr_env* e, const float* params, int n_choices, c
     if (n_episodes < 1) return refuse(who, "n_episodes must be at least 1");
     if (const int rc = disc_handle_ok(who, e); rc != RR_OK) return rc;
     return evaluate(e, who, params, precision, n_episodes, max_steps, out, false, nullptr, obs, stream, false, &H);
+}
+
+int rr_rollout_collect_discrete_stats(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                                      uint64_t seed, const uint64_t* iter, int n_steps, double gamma,
+                                      double gae_lambda, float* buf_obs, float* buf_action, float* buf_value,
+                                      float* buf_log_prob, float* buf_start, float* buf_reward, float* buf_advantage,
+                                      float* buf_return, float* last_value, float* last_done, float* last_start,
+                                      float* obs, float* reward, uint8_t* done, uint8_t* truncated, float* terms,
+                                      const rr_rollout_stats* stats, void* stream)
+{
+    // rr_rollout_collect_discrete's refusals, then rr_rollout_collect_stats's; the arguments before the handle
+    const char* who = "rr_rollout_collect_discrete_stats";
+    DiscHead H;
+    if (const int rc = disc_head_args(who, params, n_choices, table, precision, H); rc != RR_OK) return rc;
+    if (n_steps <= 0) return refuse(who, "n_steps must be positive");
+    if (!stats || !stats->partials || !stats->out)
+        return refuse(who, "stats, stats->partials and stats->out must not be null");
+    if (((uintptr_t)stats->partials & 127) != 0) return refuse(who, "stats->partials must be 128-B aligned");
+    if ((((uintptr_t)stats->out | (uintptr_t)stats->accum) & 7) != 0)
+        return refuse(who, "stats->out and stats->accum must be 8-B aligned");
+    if (!buf_advantage || !buf_return)
+        return refuse(who, "buf_advantage and buf_return are required (the sample sums follow the GAE scan)");
+    RolloutIO io = rollout_io(buf_obs, buf_action, buf_value, buf_log_prob, buf_start, buf_reward, obs, reward, done,
+                              truncated, terms);
+    if (const int rc = disc_rollout_bufs_ok(who, iter, io); rc != RR_OK) return rc;
+    if (const int rc = disc_handle_ok(who, e); rc != RR_OK) return rc;
+    if (!(e->p.flags & RR_FLAG_EPISODE_STATS))
+        return refuse(who, "the handle needs RR_FLAG_EPISODE_STATS (the running return crosses launches)");
+    if (!(e->p.flags & RR_FLAG_AUTO_RESET))
+        return refuse(who, "the handle needs RR_FLAG_AUTO_RESET (episodes follow one another)");
+    collect_io(io, n_steps, gamma, gae_lambda, buf_advantage, buf_return, last_value, last_done, last_start);
+    const CollectStatsIO sio = {(uint64_t*)stats->partials, (uint64_t*)stats->out, (uint64_t*)stats->accum,
+                                (uint32_t)rr_rollout_stats_rows(e->n)};
+    return launch_rollout(e, who, true, params, precision, seed, iter, io, stream, &sio, &H);
+}
+
+int rr_policy_evaluate_discrete_trace(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                                      int n_episodes, int64_t max_steps, const rr_eval_out* out,
+                                      const rr_eval_trace* trace, int32_t* choice, float* obs, void* stream)
+{
+    // rr_policy_evaluate_discrete's refusals, then rr_policy_evaluate_trace's; the arguments before the handle
+    const char* who = "rr_policy_evaluate_discrete_trace";
+    DiscHead H;
+    if (const int rc = disc_head_args(who, params, n_choices, table, precision, H); rc != RR_OK) return rc;
+    if (!out || !out->episodes) return refuse(who, "params, out and out->episodes must not be null");
+    if (n_episodes < 1) return refuse(who, "n_episodes must be at least 1");
+    if (!trace) return refuse(who, "trace must not be null");
+    if (!trace->slot || !trace->state || !trace->length)
+        return refuse(who, "trace->slot, trace->state and trace->length must not be null");
+    if (trace->n_slots < 1 || trace->steps < 1) return refuse(who, "trace->n_slots and trace->steps must be at least 1");
+    if (((uintptr_t)choice & 3) != 0) return refuse(who, "choice must be 4-B aligned");
+    if (const int rc = disc_handle_ok(who, e); rc != RR_OK) return rc;
+    return evaluate(e, who, params, precision, n_episodes, max_steps, out, true, trace, obs, stream, false, &H, choice);
 }
 
 int rr_ppo_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes)

@@ -20,6 +20,8 @@
 // head of the reference's DiscreteActions3DOF: the pi tower's NH = 4 heads are logits, of which the
 // first n_choices count, the sample region is discrete_act_kernel's (one uniform draw, the index, the
 // table row) and buf_act holds one float per sample, the index. Not defined: the Gaussian head.
+// Both at once (collect_stats_discrete/rocket_collect_stats_discrete.hip: rollout_discrete_stats_kernel, with
+// rollout_discrete_kernel's arguments and sio) need no region of their own: the two sets share no line.
     constexpr int NS = Dims<MODEL>::NS, NA = Dims<MODEL>::NA, NT = Dims<MODEL>::NT, EV = Dims<MODEL>::EV;
     constexpr int EPW = rol::Shape<NTW>::kEPW, NWV = rol::Shape<NTW>::kWaves;
 #ifdef RR_DISCRETE_HEAD

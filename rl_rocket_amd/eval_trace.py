@@ -1,4 +1,5 @@
-"""Recorded episodes of the one-launch evaluation (``rr_policy_evaluate_trace``).
+"""Recorded episodes of the one-launch evaluation (``rr_policy_evaluate_trace``; for a Categorical
+policy ``rr_policy_evaluate_discrete_trace``, which adds the plane of chosen indices).
 
 ``EvalTrace`` holds the device tensors the recording evaluation writes for the chosen envs;
 ``EpisodeRecord`` is one of their episodes on the host, with what the reference's env and
@@ -21,14 +22,18 @@ class EpisodeRecord:
     t + 1 the un-reset state after step t: ``SIM.states``), ``actions`` [L, na] (the clipped mean
     actions the env stepped with, normalised), ``terms`` [L, nt] and ``rewards`` [L], float32.
     ``complete`` is False for an episode cut by ``max_steps`` (``partial=True``) or by the
-    recording capacity (``clipped=True``); ``length`` is the number of steps the episode took."""
+    recording capacity (``clipped=True``); ``length`` is the number of steps the episode took.
+    ``choices`` [L] (int32) are the indices of a Categorical policy's choices, whose table rows
+    ``actions`` holds; None for a Gaussian policy."""
 
-    def __init__(self, cfg, states, actions, terms, rewards, env_id=None, episode=0, length=None, complete=True):
+    def __init__(self, cfg, states, actions, terms, rewards, env_id=None, episode=0, length=None, complete=True,
+                 choices=None):
         self.cfg = cfg
         self.states = np.asarray(states, dtype=np.float32)
         self.actions = np.asarray(actions, dtype=np.float32)
         self.terms = np.asarray(terms, dtype=np.float32)
         self.rewards = np.asarray(rewards, dtype=np.float32)
+        self.choices = None if choices is None else np.asarray(choices, dtype=np.int32)
         self.env_id, self.episode, self.complete = env_id, episode, complete
         self.length = len(self.rewards) if length is None else int(length)
         six = cfg.model == 6
@@ -150,11 +155,13 @@ class EvalTrace:
     reward terms, then the reward), ``length`` [ne, K] (steps episode k of slot s took; above S where
     the record was clipped) and ``env_ids`` [K] (slot s records env ``env_ids[s]``). ``episodes``
     (the evaluator's [n] count of completed episodes, or None) tells a finished episode from one cut
-    by ``max_steps``. Rows past an episode's length are not written."""
+    by ``max_steps``. ``choice`` [K, ne, S] (int32; None for a Gaussian policy) holds, beside each action
+    row of a Categorical policy, the index of the table row it is. Rows past an episode's length are not
+    written."""
 
-    def __init__(self, cfg, state, action, terms, length, env_ids, episodes=None):
+    def __init__(self, cfg, state, action, terms, length, env_ids, episodes=None, choice=None):
         self.cfg, self.state, self.action, self.terms, self.length = cfg, state, action, terms, length
-        self.env_ids, self.episodes = env_ids, episodes
+        self.env_ids, self.episodes, self.choice = env_ids, episodes, choice
         self._slot = {int(e): s for s, e in enumerate(torch.as_tensor(env_ids).cpu().tolist())}
 
     @property
@@ -177,7 +184,8 @@ class EvalTrace:
         # one device-to-host copy: the length, the episodes count and the episode's rows
         flat = torch.cat([self.length[k, s].reshape(1).float(), torch.as_tensor(done, device=self.length.device)
                           .reshape(1).float(), self.state[s, k].reshape(-1), self.action[s, k].reshape(-1),
-                          self.terms[s, k].reshape(-1)]).cpu().numpy()
+                          self.terms[s, k].reshape(-1)] +
+                         ([] if self.choice is None else [self.choice[s, k].float()])).cpu().numpy()  # < 2^24: exact
         length, done = int(flat[0]), int(flat[1])
         if k > done or (k == done and not partial):
             raise ValueError("env %d did not finish episode %d within max_steps (%d finished)%s" % (
@@ -193,5 +201,7 @@ class EvalTrace:
         ac = flat[o:o + cap * na].reshape(cap, na)[:n]
         o += cap * na
         tm = flat[o:o + cap * nt1].reshape(cap, nt1)[:n]
+        o += cap * nt1
+        ch = None if self.choice is None else flat[o:o + cap][:n].astype(np.int32)
         return EpisodeRecord(self.cfg, st.copy(), ac.copy(), tm[:, :-1].copy(), tm[:, -1].copy(), env_id=int(env_id),
-                             episode=k, length=length, complete=(k < done and length <= cap))
+                             episode=k, length=length, complete=(k < done and length <= cap), choices=ch)

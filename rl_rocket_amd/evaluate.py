@@ -97,8 +97,12 @@ class PolicyEvaluator:
     ONE launch (``rr_policy_evaluate_discrete``: the evaluation kernel's loop with the argmax of the
     logits, the lowest index on a tie, and the table row), on a CUDA batch with an RK4 / Euler
     integrator, 64x64 towers and 2 .. 4 choices. Where two logits lie within the fp32 towers' error of
-    each other the two paths may pick different rows. ``record=`` and a ``policy_dtype`` other than
-    "fp32" raise for it."""
+    each other the two paths may pick different rows. ``record=`` records on either path: with
+    ``fused=True`` in the same single launch (``rr_policy_evaluate_discrete_trace``), otherwise in the
+    step-by-step loop; the recorded action rows are the table rows the env stepped with, and
+    ``EvalTrace.choice`` [K, ne, S] (int32) holds their indices, from which ``Demonstrations.from_trace``
+    builds the ``[M, 1]`` index demonstrations of ``rr_bc_update_discrete``. A ``policy_dtype`` other than
+    "fp32" raises for it."""
 
     def __init__(self, batch, policy, n_episodes=5, max_steps=None, policy_dtype="fp32", fused=None, record=None,
                  record_steps=None):
@@ -111,9 +115,8 @@ class PolicyEvaluator:
         if self._discrete:
             if ns != 7 or na != 2:
                 raise ValueError("a Categorical policy drives the 3DOF env (its table rows are [gimbal, thrust])")
-            if record is not None:
-                raise ValueError("record= is not available for a Categorical policy: neither of its evaluation "
-                                 "paths records")
+            if record is not None and not hasattr(batch, "params"):
+                raise ValueError("record= needs a RocketBatch (its params hold the integrator and the TimeLimit)")
             if policy_dtype != "fp32" and policy_dtype in POLICY_PRECISIONS:
                 raise ValueError("policy_dtype=%r is not available for a Categorical policy: it is evaluated on "
                                  "fp32 towers" % policy_dtype)
@@ -177,6 +180,7 @@ class PolicyEvaluator:
                 self._trace_io = _lib.RrEvalTrace(self._slot.data_ptr(), tr.state.shape[0], tr.steps,
                                                   tr.state.data_ptr(), tr.action.data_ptr(), tr.terms.data_ptr(),
                                                   tr.length.data_ptr())
+                self._choice = tr.choice.data_ptr() if tr.choice is not None else None
             return
         from .batch import RocketBatch
         from .params import INTEGRATORS
@@ -221,7 +225,9 @@ class PolicyEvaluator:
         return EvalTrace(env.cfg, torch.zeros((k, ne, steps + 1, env.state_dim), **f32),
                          torch.zeros((k, ne, steps, env.action_dim), **f32),
                          torch.zeros((k, ne, steps, env.n_terms + 1), **f32),
-                         torch.zeros((ne, k), dtype=torch.int32, device=dev), ids.to(dev), episodes=self.episodes)
+                         torch.zeros((ne, k), dtype=torch.int32, device=dev), ids.to(dev), episodes=self.episodes,
+                         choice=torch.zeros((k, ne, steps), dtype=torch.int32, device=dev)
+                         if getattr(self, "_discrete", False) else None)  # a Categorical policy's indices
 
     @torch.no_grad()
     def run(self):
@@ -234,6 +240,12 @@ class PolicyEvaluator:
 
         env = self.env
         stream = ctypes.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
+        if self.trace is not None and self._discrete:
+            _lib.check(self._lib.rr_policy_evaluate_discrete_trace(
+                env._h, _ptr(self._pack.pack()), self.policy.n_choices, self._table, self._pack.prec, self.n_episodes,
+                self.max_steps, ctypes.byref(self._out), ctypes.byref(self._trace_io), self._choice, _ptr(env.obs),
+                stream), "rr_policy_evaluate_discrete_trace")
+            return self.result
         if self.trace is not None:
             _lib.check(self._lib.rr_policy_evaluate_trace(env._h, _ptr(self._pack.pack()), self._pack.prec,
                                                           self.n_episodes, self.max_steps, ctypes.byref(self._out),
@@ -306,7 +318,8 @@ class PolicyEvaluator:
         for _ in range(self.max_steps):
             active = ep < ne
             if self._discrete:  # the table row of the most probable choice
-                act = self.policy.continuous(self.policy.mode(self._mean(obs)))
+                idx = self.policy.mode(self._mean(obs))
+                act = self.policy.continuous(idx)
             else:
                 act = torch.clamp(self._mean(obs), -1.0, 1.0)
             (sh.set_state64 if self._dopri else sh.set_state)(pre[0], v0=pre[1], elapsed=pre[2] & el_mask)
@@ -332,6 +345,8 @@ class PolicyEvaluator:
                 kw, ew, tw = ks[w], ep_r[w], t_rec[w]
                 tr.state[kw, ew, tw + 1] = y1[:, ids].T[w]
                 tr.action[kw, ew, tw] = act[ids][w]
+                if tr.choice is not None:
+                    tr.choice[kw, ew, tw] = idx[ids][w].to(torch.int32)
                 tr.terms[kw, ew, tw] = torch.cat([terms[:nt, ids].T, rew[ids, None]], dim=1)[w]
                 t_rec = t_rec + act_r.to(t_rec.dtype)
                 tr.length[ep_r[end_r], ks[end_r]] = t_rec[end_r].to(torch.int32)

@@ -65,8 +65,12 @@ class DeviceRollout:
     step, then ``rr_policy_bootstrap`` and ``rr_gae``; both give bitwise the two-launch rollout. They
     need a batch on a CUDA device, an RK4 / Euler integrator, 64x64 towers and 2 .. 4 choices.
     ``one_launch`` stays False by default here (unlike the Gaussian policy's) until a later change
-    flips it. ``stats=True`` and a ``policy_dtype`` other than "fp32" raise. ``fused=False`` samples
-    with ``torch.multinomial`` on ``generator``."""
+    flips it. ``stats=True`` with ``one_launch=True`` (and not ``per_step``) is
+    ``rr_rollout_collect_discrete_stats``: the same launch with the Gaussian policy's accounting, ``ro.stats``
+    the same ``RolloutStats``, the rollout bitwise ``rr_rollout_collect_discrete``'s; ``stats=True`` without
+    ``one_launch=True`` or with ``per_step=True`` raises, as does a batch without ``episode_stats=True`` and
+    ``auto_reset=True``. A ``policy_dtype`` other than "fp32" raises. ``fused=False`` samples with
+    ``torch.multinomial`` on ``generator``."""
 
     def __init__(self, batch, policy, n_steps=16, gamma=0.99, gae_lambda=0.95, generator=None, fused=None,
                  seed=0, policy_dtype="fp32", one_launch=None, per_step=False, stats=False):
@@ -78,10 +82,16 @@ class DeviceRollout:
             if ns != 7 or na != 2:
                 raise ValueError("a Categorical policy drives the 3DOF env (its table rows are [gimbal, thrust]): "
                                  "a 6DOF batch is refused")
-            what = "stats=True" if stats else "policy_dtype=%r" % policy_dtype if policy_dtype != "fp32" else None
-            if what:
-                raise ValueError("%s is not available for a Categorical policy: it collects on fp32 towers, and "
-                                 "the collect statistics have no Categorical head" % what)
+            if policy_dtype != "fp32":
+                raise ValueError("policy_dtype=%r is not available for a Categorical policy: it collects on fp32 "
+                                 "towers" % policy_dtype)
+            if stats:  # rr_rollout_collect_discrete_stats: the one-launch collect only, on a real batch
+                if not hasattr(batch, "params"):
+                    raise ValueError("stats=True needs a RocketBatch (its params hold the integrator and the "
+                                     "episode_stats / auto_reset flags)")
+                if not one_launch or per_step:
+                    raise ValueError("stats=True for a Categorical policy needs one_launch=True without per_step=True "
+                                     "(rr_rollout_collect_discrete_stats); its default collect is the two-launch one")
             opt = "one_launch=True" if one_launch else "per_step=True" if per_step and one_launch is None else None
             if opt:  # the opt-in launches of the discrete-rollout unit
                 if torch.device(batch.device).type != "cuda":
@@ -159,10 +169,12 @@ class DeviceRollout:
             self._act, self._act_shape, self._boot_na = "rr_policy_act", (ns, na), na
             # the one-launch and per-step calls, and what they take between params and the precision
             self._collect, self._step, self._head = "rr_rollout_collect", "rr_rollout_step", ()
+            self._collect_stats = "rr_rollout_collect_stats"
             if self.discrete:  # the host table the discrete calls copy into their launch; the 4-head image's (7, 4)
                 table = (ctypes.c_float * (2 * policy.n_choices))(*policy.table.reshape(-1).tolist())
                 self._act, self._act_shape, self._boot_na = "rr_policy_act_discrete", (ns, policy.n_choices, table), 4
                 self._collect, self._step = "rr_rollout_collect_discrete", "rr_rollout_step_discrete"
+                self._collect_stats = "rr_rollout_collect_discrete_stats"
                 self._head = (policy.n_choices, table)
             bufs = _lib.RrBuffers()
             _lib.check(self._lib.rr_get_buffers(batch._h, ctypes.byref(bufs)), "rr_get_buffers")
@@ -225,13 +237,13 @@ class DeviceRollout:
         prec = self._pack.prec
         if self.stats is not None:
             st = self.stats.struct()
-            _lib.check(lib.rr_rollout_collect_stats(env._h, params, prec, self.seed, it, self.n_steps, self.gamma,
-                                                    self.lam, p(self.obs), p(self.actions), p(self.values),
-                                                    p(self.log_probs), p(self.starts), p(self.rewards),
-                                                    p(self.advantages), p(self.returns), p(self.last_value),
-                                                    p(self.last_done), p(self.last_start), obs, p(env.reward), done,
-                                                    p(env.truncated), p(env.terms), c.byref(st), stream),
-                       "rr_rollout_collect_stats")
+            _lib.check(getattr(lib, self._collect_stats)(env._h, params, *self._head, prec, self.seed, it, self.n_steps,
+                                                         self.gamma, self.lam, p(self.obs), p(self.actions),
+                                                         p(self.values), p(self.log_probs), p(self.starts),
+                                                         p(self.rewards), p(self.advantages), p(self.returns),
+                                                         p(self.last_value), p(self.last_done), p(self.last_start),
+                                                         obs, p(env.reward), done, p(env.truncated), p(env.terms),
+                                                         c.byref(st), stream), self._collect_stats)
             self.iter.add_(1)
             return
         if self.one_launch and not self.per_step:
