@@ -541,6 +541,30 @@ int rr_policy_evaluate_trace(rr_env* e, const float* params, int precision, int 
 int rr_policy_evaluate_exact(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
                              const rr_eval_out* out, float* obs /* [n][state_dim] or NULL */, void* stream);
 
+/* ---- Recording whole episodes in the one-launch exact-mode evaluation (ABI 14, added without a
+ * version bump: a new symbol, nothing existing changes) ----
+ * What the reference's make_eval_env computes: Monitor(RecordVideo(EpisodeAnalyzer(TimeLimit(env))))
+ * under a deterministic policy, stepped by the reference's own integrator, with the EpisodeAnalyzer's
+ * histories of the envs the caller chooses. rr_policy_evaluate_exact_trace IS rr_policy_evaluate_exact
+ * (same arithmetic in the same order, same reset draws, same rr_eval_out rows, the same state64,
+ * float32 planes, v0, counter words and running returns left in the handle) and additionally writes
+ * the records of rr_policy_evaluate_trace into the same rr_eval_trace, by the contract stated there
+ * (slots, t counted from this call, capacity clipping, partial lengths, untouched rows, 64-bit row
+ * indices). In this mode, for step t of episode k of the env with slot s:
+ *   state [s][k][t + 1][:]  float32 of the fp64 state after the quaternion renormalisation (3DOF:
+ *                           the angle wrap) and before any reset: the values final_state holds for
+ *                           the episode's last step; row 0 is float32(state64) at the call (k = 0)
+ *                           or the auto-reset draw (k > 0)
+ *   action[s][k][t][:]      the clipped mean action the solver stepped with
+ *   terms [s][k][t][:]      the float32 reward terms rr_step stores, followed by the reward (with
+ *                           RR_FLAG_REWARD_ANNEALING the annealed reward, the terms unchanged)
+ * RR_EINVAL: as rr_policy_evaluate_exact (RK4 / Euler handles go to rr_policy_evaluate_trace), and
+ * trace, trace->slot, trace->state or trace->length NULL, n_slots < 1, steps < 1. Asynchronous,
+ * capturable, no allocation. */
+int rr_policy_evaluate_exact_trace(rr_env* e, const float* params, int precision, int n_episodes,
+                                   int64_t max_steps, const rr_eval_out* out, const rr_eval_trace* trace,
+                                   float* obs, void* stream);
+
 /* RolloutBuffer.compute_returns_and_advantage: rewards / values / starts [T][n] (starts[t]
  * = episode-start flag of step t), last_value / last_done [n] -> advantages, returns [T][n].
  * The backward scan runs in fp64 (gamma, lam doubles since ABI 13) and each stored value is

@@ -200,6 +200,8 @@ SIGNATURES = {
                                                 ctypes.POINTER(RrEvalOut), ctypes.POINTER(RrEvalTrace), _P, _P]),
     "rr_policy_evaluate_exact": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                                 ctypes.POINTER(RrEvalOut), _P, _P]),
+    "rr_policy_evaluate_exact_trace": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                                      ctypes.POINTER(RrEvalOut), ctypes.POINTER(RrEvalTrace), _P, _P]),
     "rr_gae": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, ctypes.c_double, ctypes.c_double, _P,
                               _P, _P]),
     "rr_clip_adam_workspace_size": (ctypes.c_int, [ctypes.c_int64, _P]),

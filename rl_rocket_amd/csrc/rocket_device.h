@@ -1217,6 +1217,9 @@ inline T from_unit(const void* p)
 extern "C" {
 __attribute__((visibility("hidden"))) int rrx_launch_exact(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrx_launch_eval_exact(const void* launch, const void* io);
+// eval_exact_trace/rocket_eval_exact_trace.hip: the recording one-launch exact-mode evaluation; launch / io as
+// rrx_launch_eval_exact, trace points to the caller's EvalTraceIO
+__attribute__((visibility("hidden"))) int rrx_launch_eval_exact_trace(const void* launch, const void* io, const void* trace);
 __attribute__((visibility("hidden"))) int rrc_launch_collect(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrc_launch_eval(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrc_launch_eval_trace(const void* launch, const void* io, const void* trace);

@@ -132,10 +132,12 @@ constexpr size_t kTraceArgOff =
     karg_up(karg_up(karg_up(karg_up(sizeof(float*) + 2 * sizeof(uint32_t), alignof(KParams)) + sizeof(KParams),
                             alignof(Bufs)) + sizeof(Bufs), alignof(EvalIO)) + sizeof(EvalIO), alignof(EvalTraceIO));
 
+// OFF: where the kernel's EvalTraceIO parameter sits (eval_exact_trace_kernel has another argument list)
+template <size_t OFF = kTraceArgOff>
 __device__ __forceinline__ TraceArgs trace_args()
 {
     typedef const __attribute__((address_space(4))) char* karg_t;
-    karg_t k = (karg_t)__builtin_amdgcn_kernarg_segment_ptr() + kTraceArgOff;
+    karg_t k = (karg_t)__builtin_amdgcn_kernarg_segment_ptr() + OFF;
     asm volatile("" : "+s"(k));
     auto ptr = [&](size_t off) { return *(const __attribute__((address_space(4))) uint64_t*)(k + off); };
     auto word = [&](size_t off) { return *(const __attribute__((address_space(4))) uint32_t*)(k + off); };

@@ -373,6 +373,7 @@ constexpr int kNoUnit = (int)hipErrorInvalidDeviceFunction;
 extern "C" {
 __attribute__((weak)) int rrx_launch_exact(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrx_launch_eval_exact(const void*, const void*) { return kNoUnit; }
+__attribute__((weak)) int rrx_launch_eval_exact_trace(const void*, const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_collect(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval_trace(const void*, const void*, const void*) { return kNoUnit; }
@@ -1580,8 +1581,9 @@ int rr_rollout_collect_stats(rr_env* e, const float* params, int precision, uint
 
 namespace {
 
-// rr_policy_evaluate (trace == nullptr), rr_policy_evaluate_trace and rr_policy_evaluate_exact (`exact`:
-// the handle must be an RR_INT_DOPRI5 one, where the other two refuse it): the argument checks, the
+// rr_policy_evaluate (trace == nullptr), rr_policy_evaluate_trace, rr_policy_evaluate_exact and
+// rr_policy_evaluate_exact_trace (`exact`: the handle must be an RR_INT_DOPRI5 one, where the other two
+// refuse it; with `traced` it records as rr_policy_evaluate_trace does): the argument checks, the
 // kernel's EvalIO and the launch. `who` prefixes every message. `head`: the Categorical policy's calls
 // (rr_policy_evaluate_discrete and, traced, rr_policy_evaluate_discrete_trace with its `choice` plane).
 int evaluate(rr_env* e, const char* who, const float* params, int precision, int n_episodes, int64_t max_steps,
@@ -1603,7 +1605,8 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
             return fail(RR_EINVAL, w + "trace->n_slots and trace->steps must be at least 1");
     }
     if (exact && e->p.integrator != RR_INT_DOPRI5)
-        return fail(RR_EINVAL, w + "RK4 / Euler envs are evaluated by rr_policy_evaluate");
+        return fail(RR_EINVAL, w + (traced ? "RK4 / Euler envs are evaluated by rr_policy_evaluate_trace"
+                                           : "RK4 / Euler envs are evaluated by rr_policy_evaluate"));
     if (!exact && e->p.integrator == RR_INT_DOPRI5)
         return fail(RR_EINVAL, w + "RR_INT_DOPRI5 envs are evaluated step by step (rr_step) or by "
                                    "rr_policy_evaluate_exact");
@@ -1645,9 +1648,10 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
     } else if (head) {  // rr_policy_evaluate_discrete (rollout_discrete/rocket_rollout_discrete.hip)
         err = (hipError_t)rrc_launch_eval_discrete(&L, &io, head);
     } else if (exact) {
-        // eval_exact_kernel (eval_exact/rocket_eval_exact.hip): eval_kernel's grid, one variant for every N
+        // eval_exact_kernel (eval_exact/rocket_eval_exact.hip): eval_kernel's grid, one variant for every N;
+        // traced: eval_exact_trace_kernel (eval_exact_trace/rocket_eval_exact_trace.hip), the same launch
         const EvalExactLaunch X = {e->p.model, prec, L.grid, e->d_xp, &b, e->state64, stream};
-        err = (hipError_t)rrx_launch_eval_exact(&X, &io);
+        err = (hipError_t)(traced ? rrx_launch_eval_exact_trace(&X, &io, &t) : rrx_launch_eval_exact(&X, &io));
     } else if (traced) {
         err = (hipError_t)rrc_launch_eval_trace(&L, &io, &t);
     } else {
@@ -1678,6 +1682,13 @@ int rr_policy_evaluate_exact(rr_env* e, const float* params, int precision, int 
 {
     return evaluate(e, "rr_policy_evaluate_exact", params, precision, n_episodes, max_steps, out, false, nullptr, obs,
                     stream, true);
+}
+
+int rr_policy_evaluate_exact_trace(rr_env* e, const float* params, int precision, int n_episodes, int64_t max_steps,
+                                   const rr_eval_out* out, const rr_eval_trace* trace, float* obs, void* stream)
+{
+    return evaluate(e, "rr_policy_evaluate_exact_trace", params, precision, n_episodes, max_steps, out, true, trace,
+                    obs, stream, true);
 }
 
 int rr_gae(int64_t T, int64_t n, const float* rewards, const float* values, const float* starts,

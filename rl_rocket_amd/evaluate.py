@@ -69,8 +69,9 @@ class PolicyEvaluator:
     registers, nothing stored per step), capturable in a graph. On an ``integrator="dopri5"`` batch
     ``fused=True`` must be asked for and is ``rr_policy_evaluate_exact``: the same loop around the exact
     solver, one launch where the step-by-step path takes two exact steps and a dozen small launches
-    per iteration, bit for bit the episodes of ``rr_policy_act`` + ``rr_step`` (it does not record:
-    ``record=`` with it raises). ``fused=False`` (any policy whose
+    per iteration, bit for bit the episodes of ``rr_policy_act`` + ``rr_step`` (``record=`` with it
+    raises unless ``record_in_launch=True`` asks for the recording launch, below).
+    ``fused=False`` (any policy whose
     ``policy(obs)[0]`` is the action mean, and the default for ``integrator="dopri5"``): the same algorithm in
     PyTorch ops, one ``batch.step`` per iteration for ``max_steps`` iterations; the un-reset terminal
     state and the reward terms of each step come from a shadow batch without auto-reset stepped
@@ -90,6 +91,16 @@ class PolicyEvaluator:
     history takes v_0 from the first recorded state: reset first, as for whole episodes.
     ``record=None`` is the plain evaluation (``rr_policy_evaluate``).
 
+    ``record_in_launch=True`` (default None: everything above as it is) records on an
+    ``integrator="dopri5"`` batch in the one launch as well (``rr_policy_evaluate_exact_trace``): the
+    reference's ``make_eval_env`` set-up, a deterministic policy stepped by the exact integrator with the
+    ``EpisodeAnalyzer``'s histories, hundreds of launches cheaper than ``fused=False, record=``. It needs
+    ``record``, ``fused=True``, a CUDA batch and the 64x64 ``MlpActorCritic``, with any ``policy_dtype``.
+    The recorded state rows are the float32 casts of the fp64 state, the terms those ``rr_step`` stores.
+    On a fused RK4 / Euler batch recording already happens in the launch and the keyword changes
+    nothing; with ``fused=False``, and for a Categorical policy on a dopri5 batch (still evaluated step
+    by step), it raises.
+
     A ``MlpCategoricalActorCritic`` (discrete 3DOF actions) takes the action
     ``policy.continuous(policy.mode(logits))``, SB3's deterministic prediction behind
     ``DiscreteActions3DOF``. By default it runs through the step-by-step path (``fused=False``, chosen
@@ -105,13 +116,21 @@ class PolicyEvaluator:
     "fp32" raises for it."""
 
     def __init__(self, batch, policy, n_episodes=5, max_steps=None, policy_dtype="fp32", fused=None, record=None,
-                 record_steps=None):
+                 record_steps=None, record_in_launch=None):
         from . import _lib
         from .params import STATE_NAMES_3DOF, STATE_NAMES_6DOF
 
         self.env, self.policy = batch, policy
         n, ns, na = batch.num_envs, batch.state_dim, batch.action_dim
         self._discrete = isinstance(policy, MlpCategoricalActorCritic)
+        if record_in_launch:  # the refusals that need nothing of the batch but its integrator
+            if record is None:
+                raise ValueError("record_in_launch=True needs record")
+            if fused is not None and not fused:
+                raise ValueError("record_in_launch=True needs fused=True (fused=False records step by step)")
+            if self._discrete and hasattr(batch, "params") and int(batch.params.integrator) == _lib.RR_INT_DOPRI5:
+                raise ValueError("record_in_launch=True is not available for a Categorical policy on an "
+                                 "integrator=\"dopri5\" batch: it is evaluated step by step there")
         if self._discrete:
             if ns != 7 or na != 2:
                 raise ValueError("a Categorical policy drives the 3DOF env (its table rows are [gimbal, thrust])")
@@ -145,9 +164,13 @@ class PolicyEvaluator:
             fused = fused_grad_supported(policy, ns, na) and not dopri
         if fused and not self._discrete and not fused_grad_supported(policy, ns, na):
             raise ValueError("fused evaluation needs an MlpActorCritic with 64x64 towers")
-        if fused and dopri and record is not None:
-            raise ValueError("record= on an integrator=\"dopri5\" batch needs fused=False (the one-launch exact "
-                             "evaluation does not record)")
+        if record_in_launch and not fused:  # fused=None resolved to the step-by-step path (a dopri5 batch)
+            raise ValueError("record_in_launch=True needs fused=True (fused=False records step by step)")
+        if fused and dopri and record is not None and not record_in_launch:
+            raise ValueError("record= on an integrator=\"dopri5\" batch needs fused=False, or "
+                             "record_in_launch=True for the recording one-launch exact evaluation")
+        if fused and dopri and record_in_launch and torch.device(batch.device).type != "cuda":
+            raise ValueError("record_in_launch=True needs a batch on a CUDA device (rr_policy_evaluate_exact_trace)")
         self.fused = bool(fused)
         self._exact = self.fused and dopri
         if policy_dtype not in POLICY_PRECISIONS:
@@ -247,10 +270,10 @@ class PolicyEvaluator:
                 stream), "rr_policy_evaluate_discrete_trace")
             return self.result
         if self.trace is not None:
-            _lib.check(self._lib.rr_policy_evaluate_trace(env._h, _ptr(self._pack.pack()), self._pack.prec,
-                                                          self.n_episodes, self.max_steps, ctypes.byref(self._out),
-                                                          ctypes.byref(self._trace_io), _ptr(env.obs), stream),
-                       "rr_policy_evaluate_trace")
+            call, name = ((self._lib.rr_policy_evaluate_exact_trace, "rr_policy_evaluate_exact_trace") if self._exact
+                          else (self._lib.rr_policy_evaluate_trace, "rr_policy_evaluate_trace"))
+            _lib.check(call(env._h, _ptr(self._pack.pack()), self._pack.prec, self.n_episodes, self.max_steps,
+                            ctypes.byref(self._out), ctypes.byref(self._trace_io), _ptr(env.obs), stream), name)
             return self.result
         if self._discrete:
             _lib.check(self._lib.rr_policy_evaluate_discrete(env._h, _ptr(self._pack.pack()), self.policy.n_choices,
@@ -369,8 +392,8 @@ class PolicyEvaluator:
 
 def evaluate_policy(policy, batch, n_eval_episodes=5, return_episode_rewards=False, **kw):
     """SB3 ``evaluate_policy(model, env, n_eval_episodes, deterministic=True)`` on a ``RocketBatch``:
-    resets every env, runs a ``PolicyEvaluator`` (``**kw``: max_steps, policy_dtype, fused) and
-    returns ``(mean_reward, std_reward)`` or, with ``return_episode_rewards``, ``(episode_rewards,
+    resets every env, runs a ``PolicyEvaluator`` (``**kw``: max_steps, policy_dtype, fused, record,
+    record_in_launch, ...) and returns ``(mean_reward, std_reward)`` or, with ``return_episode_rewards``, ``(episode_rewards,
     episode_lengths)`` as lists over the finished episodes.
 
     ``n_eval_episodes`` is PER ENV here: every env runs that many episodes, N * n_eval_episodes in

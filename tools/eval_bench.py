@@ -26,6 +26,16 @@
   step_exact_kernel launch (profiles/r06/r06h/: 25.9 us) as the "launch overhead removed, slowest
   wave of every step kept" yardstick. `fixed`: 64 steps of every env in one launch against 64 x
   (rr_policy_act + rr_step), the same work bit for bit (exact_fixed_work).
+
+    python tools/eval_bench.py --integrator dopri5 --record [--out profiles/eval_exact_trace/eval_exact_trace_bench.json]
+
+  the recording one-launch exact evaluation (rr_policy_evaluate_exact_trace) on the same workload,
+  four legs alternating in one session, each on a batch of its own with the same seed and from the
+  same reset, `--reps` timed runs each after a warm-up run (the three one-launch legs in rotating
+  order, then the step-by-step leg): (a) `plain`, rr_policy_evaluate_exact;
+  (b) `record_64`, the new call with 64 envs recorded, one per wave spread over the grid (env
+  j * n / 64 + j); (c) `record_all`, every env recorded, with the bytes of rows it wrote; (d)
+  `stepwise_64`, PolicyEvaluator(fused=False, record=) of the same 64 envs.
 """
 import argparse
 import json
@@ -57,6 +67,7 @@ def main():
     ap.add_argument("--no-unfused", action="store_true")
     ap.add_argument("--integrator", choices=("rk4", "dopri5"), default="rk4")
     ap.add_argument("--tl", type=int, default=800, help="TimeLimit of the dopri5 leg")
+    ap.add_argument("--record", action="store_true", help="the dopri5 leg's recording comparison")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -83,7 +94,7 @@ def main():
                 f.write(json.dumps(rec, indent=1) + "\n")
 
     if args.integrator == "dopri5":
-        write(exact_leg(args, rec, dev))
+        write(exact_trace_leg(args, rec, dev) if args.record else exact_leg(args, rec, dev))
         return
 
     def env():
@@ -188,6 +199,69 @@ def exact_leg(args, rec, dev):
                yardstick_us=yard, yardstick="%d x %.1f us (one step_exact_kernel launch, profiles/r06/r06h/)"
                % (tl, STEP_EXACT_US), yardstick_over_fused=yard / f["us_median"])
     rec["fixed"] = exact_fixed_work(args, dev, pol)
+    return rec
+
+
+def exact_trace_leg(args, rec, dev):
+    """The --integrator dopri5 --record record (see the module docstring)."""
+    import torch
+    from rl_rocket_amd.batch import RocketBatch
+    from rl_rocket_amd.params import ENV_CONFIG_6DOF
+    from rl_rocket_amd.rollout import PolicyEvaluator
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from rollout_ref import scaled_policy
+
+    n, tl = args.n, args.tl
+    if n % 64 or args.reps < 5:
+        raise SystemExit("--record needs n a multiple of 64 and --reps >= 5")
+    pol = scaled_policy(14, 3, seed=5, head_scale=1.0).to(dev)
+    ids64 = [j * (n // 64) + j for j in range(64)]  # lane j of every (n / 4096)-th wave
+    rec.update(integrator="dopri5", max_episode_steps=tl, policy="tests/rollout_ref.scaled_policy(14, 3, seed=5, "
+               "head_scale=1.0)", n_episodes=1, reps=args.reps, recorded_64=ids64)
+    legs = {}
+    for name, kw in (("plain", dict(fused=True)),
+                     ("record_64", dict(fused=True, record=ids64, record_in_launch=True)),
+                     ("record_all", dict(fused=True, record=torch.arange(n), record_in_launch=True)),
+                     ("stepwise_64", dict(fused=False, record=ids64))):
+        b = RocketBatch(n, model=6, device=dev, max_episode_steps=tl, integrator="dopri5",
+                        **dict(ENV_CONFIG_6DOF, seed=1234))
+        legs[name] = (b, PolicyEvaluator(b, pol, n_episodes=1, **kw), [])
+    one = ["plain", "record_64", "record_all"]
+    for r in range(args.reps + 1):  # run 0 is the warm-up; the legs alternate, each from the same reset
+        # the one-launch legs rotate, so that each of them follows the long step-by-step leg in turn
+        order = one[r % 3:] + one[:r % 3] + ["stepwise_64"]
+        for pos, name in enumerate(order):
+            b, e, runs = legs[name]
+            b.reset()
+            torch.cuda.synchronize()
+            us = timed(e.run, 1)
+            ln = e.result.ep_length[0].long()
+            waves = torch.nn.functional.pad(ln, (0, (-n) % 64)).view(-1, 64).max(dim=1).values
+            row = {"us": us, "position_in_round": pos, "env_steps": int(ln.sum()), "wave_steps_max": int(waves.max()),
+                   "unfinished": int((e.result.episodes < 1).sum())}
+            if e.trace is not None:  # rows written: length + 1 state rows, length action and terms rows, the length word
+                tr = e.trace
+                L = tr.length[0].long().clamp(max=tr.steps)
+                per_step = 4 * (tr.state.shape[-1] + tr.action.shape[-1] + tr.terms.shape[-1])
+                row.update(recorded_env_steps=int(L.sum()),
+                           trace_bytes=int(L.sum()) * per_step + L.numel() * (4 * tr.state.shape[-1] + 4),
+                           lengths_equal_ep_length=bool(torch.equal(tr.length[0].long(), ln[tr.env_ids])))
+            if r:
+                runs.append(row)
+    for name, (b, e, runs) in legs.items():
+        us = [x["us"] for x in runs]
+        rec[name] = {"runs": runs, "us_median": statistics.median(us), "us_min": min(us), "us_max": max(us)}
+        b.close()
+    a = rec["plain"]
+    spread = a["us_max"] - a["us_min"]
+    rec["plain_spread_us"] = spread
+    for name in ("record_64", "record_all", "stepwise_64"):
+        x = rec[name]
+        x["over_plain_median_us"] = x["us_median"] - a["us_median"]
+        x["median_over_plain_max_us"] = x["us_median"] - a["us_max"]
+        x["exceeds_plain_max_by_more_than_its_spread"] = bool(x["us_median"] - a["us_max"] > spread)
+    rec["stepwise_over_record_64"] = rec["stepwise_64"]["us_median"] / rec["record_64"]["us_median"]
     return rec
 
 
