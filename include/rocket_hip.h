@@ -929,6 +929,31 @@ int rr_policy_evaluate_discrete_trace(rr_env* e, const float* params, int n_choi
                                       int n_episodes, int64_t max_steps, const rr_eval_out* out,
                                       const rr_eval_trace* trace, int32_t* choice, float* obs, void* stream);
 
+/* ---- The Categorical policy's evaluation under the exact integrator in ONE launch (a pure addition
+ * to ABI 14: a new symbol, nothing existing changes) ----
+ * The reference's sensitivity_test.py set-up: evaluate_policy on
+ * TimeLimit(DiscreteActions3DOF(RewardAnnealing(Rocket))), a deterministic Discrete(K) policy stepped by
+ * the reference's own integrator (scipy RK45 with the brentq ground event). The argument list is
+ * rr_policy_evaluate_discrete's, the semantics are rr_policy_evaluate_exact's: a step is
+ * obs = float32(float32(state64) / normalizer), the pi tower and its logits, the action
+ * table[argmax_k<K z_k] (the lowest index on a tie, NOT clipped), the adaptive solve, reward (with
+ * RR_FLAG_REWARD_ANNEALING the annealed one, its thrust the table row's), TimeLimit and auto-reset; the
+ * fp64 state, v0, counter word and running return stay in registers between steps. Where the softmax is
+ * saturated so that the sampled index is the argmax, the call writes bitwise the episodes
+ * rr_policy_act_discrete + rr_step run (tests/test_gpu_eval_exact_discrete.py), and it leaves state64,
+ * the float32 state planes, v0, the counter words and the running returns as that many rr_step calls.
+ * Rows, flags, max_steps, obs, the untouched done list are rr_policy_evaluate_exact's. Asynchronous,
+ * capturable, no allocation.
+ * RR_EINVAL before any HIP call, with a message that starts with the function's name: everything
+ * rr_policy_evaluate_discrete refuses (a NULL handle / params / out / out->episodes, a 6DOF handle, a
+ * precision other than RR_POLICY_FP32, n_choices outside 2 .. 4, a NULL table or a non-finite entry in
+ * its first n_choices rows, params not 16-B aligned, no RR_FLAG_AUTO_RESET, n_episodes < 1, no TimeLimit
+ * with max_steps 0), except that the handle must be an RR_INT_DOPRI5 one (RK4 / Euler handles go to
+ * rr_policy_evaluate_discrete). The argument checks come before the handle is read. */
+int rr_policy_evaluate_exact_discrete(rr_env* e, const float* params, int n_choices, const float* table,
+                                      int precision, int n_episodes, int64_t max_steps, const rr_eval_out* out,
+                                      float* obs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1220,6 +1220,9 @@ __attribute__((visibility("hidden"))) int rrx_launch_eval_exact(const void* laun
 // eval_exact_trace/rocket_eval_exact_trace.hip: the recording one-launch exact-mode evaluation; launch / io as
 // rrx_launch_eval_exact, trace points to the caller's EvalTraceIO
 __attribute__((visibility("hidden"))) int rrx_launch_eval_exact_trace(const void* launch, const void* io, const void* trace);
+// eval_exact_discrete/rocket_eval_exact_discrete.hip: the Categorical policy's one-launch exact-mode evaluation;
+// launch / io as rrx_launch_eval_exact, head points to the caller's DiscHead
+__attribute__((visibility("hidden"))) int rrx_launch_eval_exact_discrete(const void* launch, const void* io, const void* head);
 __attribute__((visibility("hidden"))) int rrc_launch_collect(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrc_launch_eval(const void* launch, const void* io);
 __attribute__((visibility("hidden"))) int rrc_launch_eval_trace(const void* launch, const void* io, const void* trace);

@@ -374,6 +374,7 @@ extern "C" {
 __attribute__((weak)) int rrx_launch_exact(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrx_launch_eval_exact(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrx_launch_eval_exact_trace(const void*, const void*, const void*) { return kNoUnit; }
+__attribute__((weak)) int rrx_launch_eval_exact_discrete(const void*, const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_collect(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval(const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval_trace(const void*, const void*, const void*) { return kNoUnit; }
@@ -1585,7 +1586,8 @@ namespace {
 // rr_policy_evaluate_exact_trace (`exact`: the handle must be an RR_INT_DOPRI5 one, where the other two
 // refuse it; with `traced` it records as rr_policy_evaluate_trace does): the argument checks, the
 // kernel's EvalIO and the launch. `who` prefixes every message. `head`: the Categorical policy's calls
-// (rr_policy_evaluate_discrete and, traced, rr_policy_evaluate_discrete_trace with its `choice` plane).
+// (rr_policy_evaluate_discrete and, traced, rr_policy_evaluate_discrete_trace with its `choice` plane; with
+// `exact` and not traced, rr_policy_evaluate_exact_discrete).
 int evaluate(rr_env* e, const char* who, const float* params, int precision, int n_episodes, int64_t max_steps,
              const rr_eval_out* out, bool traced, const rr_eval_trace* trace, float* obs, void* stream,
              bool exact = false, const DiscHead* head = nullptr, int32_t* choice = nullptr)
@@ -1643,7 +1645,11 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
         t.n_slots = trace->n_slots;
         t.steps = trace->steps;
     }
-    if (head && traced) {  // rr_policy_evaluate_discrete_trace (eval_trace_discrete/)
+    if (head && exact && !traced) {
+        // rr_policy_evaluate_exact_discrete: eval_exact_discrete_kernel (eval_exact_discrete/), eval_exact_kernel's launch
+        const EvalExactLaunch X = {e->p.model, prec, L.grid, e->d_xp, &b, e->state64, stream};
+        err = (hipError_t)rrx_launch_eval_exact_discrete(&X, &io, head);
+    } else if (head && traced) {  // rr_policy_evaluate_discrete_trace (eval_trace_discrete/)
         err = (hipError_t)rrc_launch_eval_discrete_trace(&L, &io, head, &t, choice);
     } else if (head) {  // rr_policy_evaluate_discrete (rollout_discrete/rocket_rollout_discrete.hip)
         err = (hipError_t)rrc_launch_eval_discrete(&L, &io, head);
@@ -2213,12 +2219,15 @@ int disc_head_args(const char* who, const float* params, int n_choices, const fl
     if (((uintptr_t)params & 15) != 0) return refuse(who, "params must be 16-B aligned");
     return RR_OK;
 }
-int disc_handle_ok(const char* who, const rr_env* e)
+// `exact`: rr_policy_evaluate_exact_discrete, which takes the RR_INT_DOPRI5 handles the others refuse
+int disc_handle_ok(const char* who, const rr_env* e, bool exact = false)
 {
     if (!e) return refuse(who, "null handle");
     if (e->p.model != RR_MODEL_3DOF)
         return refuse(who, "a 6DOF handle is refused: the table rows are [gimbal, thrust] of the 3DOF env");
-    if (e->p.integrator == RR_INT_DOPRI5)
+    if (exact && e->p.integrator != RR_INT_DOPRI5)
+        return refuse(who, "RK4 / Euler envs are evaluated by rr_policy_evaluate_discrete");
+    if (!exact && e->p.integrator == RR_INT_DOPRI5)
         return refuse(who, "RR_INT_DOPRI5 envs step through rr_policy_act_discrete + rr_step");
     return RR_OK;
 }
@@ -2281,6 +2290,20 @@ int rr_policy_evaluate_discrete(rr_env* e, const float* params, int n_choices, c
     if (n_episodes < 1) return refuse(who, "n_episodes must be at least 1");
     if (const int rc = disc_handle_ok(who, e); rc != RR_OK) return rc;
     return evaluate(e, who, params, precision, n_episodes, max_steps, out, false, nullptr, obs, stream, false, &H);
+}
+
+int rr_policy_evaluate_exact_discrete(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                                      int n_episodes, int64_t max_steps, const rr_eval_out* out, float* obs,
+                                      void* stream)
+{
+    // rr_policy_evaluate_discrete's refusals with the integrator's turned round; the arguments before the handle
+    const char* who = "rr_policy_evaluate_exact_discrete";
+    DiscHead H;
+    if (const int rc = disc_head_args(who, params, n_choices, table, precision, H); rc != RR_OK) return rc;
+    if (!out || !out->episodes) return refuse(who, "params, out and out->episodes must not be null");
+    if (n_episodes < 1) return refuse(who, "n_episodes must be at least 1");
+    if (const int rc = disc_handle_ok(who, e, true); rc != RR_OK) return rc;
+    return evaluate(e, who, params, precision, n_episodes, max_steps, out, false, nullptr, obs, stream, true, &H);
 }
 
 int rr_rollout_collect_discrete_stats(rr_env* e, const float* params, int n_choices, const float* table, int precision,

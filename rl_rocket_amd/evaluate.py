@@ -98,8 +98,8 @@ class PolicyEvaluator:
     ``record``, ``fused=True``, a CUDA batch and the 64x64 ``MlpActorCritic``, with any ``policy_dtype``.
     The recorded state rows are the float32 casts of the fp64 state, the terms those ``rr_step`` stores.
     On a fused RK4 / Euler batch recording already happens in the launch and the keyword changes
-    nothing; with ``fused=False``, and for a Categorical policy on a dopri5 batch (still evaluated step
-    by step), it raises.
+    nothing; with ``fused=False``, and for a Categorical policy on a dopri5 batch (recorded step by
+    step only), it raises.
 
     A ``MlpCategoricalActorCritic`` (discrete 3DOF actions) takes the action
     ``policy.continuous(policy.mode(logits))``, SB3's deterministic prediction behind
@@ -107,8 +107,14 @@ class PolicyEvaluator:
     automatically; the default stays there until a later change flips it). ``fused=True`` is opt-in:
     ONE launch (``rr_policy_evaluate_discrete``: the evaluation kernel's loop with the argmax of the
     logits, the lowest index on a tie, and the table row), on a CUDA batch with an RK4 / Euler
-    integrator, 64x64 towers and 2 .. 4 choices. Where two logits lie within the fp32 towers' error of
-    each other the two paths may pick different rows. ``record=`` records on either path: with
+    integrator, 64x64 towers and 2 .. 4 choices. On an ``integrator="dopri5"`` batch ``fused=True`` is
+    ``rr_policy_evaluate_exact_discrete``: the same head in the exact evaluation's loop, the reference's
+    ``sensitivity_test.py`` set-up (``evaluate_policy`` on ``TimeLimit(DiscreteActions3DOF(RewardAnnealing(
+    Rocket)))`` under scipy RK45 + brentq) in one launch, bit for bit the episodes of
+    ``rr_policy_act_discrete`` + ``rr_step`` where the sampled index is the argmax; ``record=`` with it
+    raises (recording stays on the step-by-step path there). Where two logits lie within the fp32 towers'
+    error of each other the two paths may pick different rows. On an RK4 / Euler batch ``record=`` records
+    on either path: with
     ``fused=True`` in the same single launch (``rr_policy_evaluate_discrete_trace``), otherwise in the
     step-by-step loop; the recorded action rows are the table rows the env stepped with, and
     ``EvalTrace.choice`` [K, ne, S] (int32) holds their indices, from which ``Demonstrations.from_trace``
@@ -142,12 +148,12 @@ class PolicyEvaluator:
             if fused:  # the opt-in launch of the discrete-rollout unit
                 if torch.device(batch.device).type != "cuda":
                     raise ValueError("fused=True for a Categorical policy needs a batch on a CUDA device "
-                                     "(rr_policy_evaluate_discrete)")
+                                     "(rr_policy_evaluate_discrete / rr_policy_evaluate_exact_discrete)")
                 if not fused_discrete_supported(policy, ns):
                     raise ValueError("fused=True needs a Categorical policy with 64x64 towers and 2 .. 4 choices")
-                if int(batch.params.integrator) == _lib.RR_INT_DOPRI5:
-                    raise ValueError("fused=True is not available for a Categorical policy on an "
-                                     "integrator=\"dopri5\" batch: it is evaluated step by step there")
+                if int(batch.params.integrator) == _lib.RR_INT_DOPRI5 and record is not None:
+                    raise ValueError("fused=True with record= is not available for a Categorical policy on an "
+                                     "integrator=\"dopri5\" batch: it is recorded step by step there")
             fused = bool(fused)
         dev = batch.device
         p = batch.params
@@ -276,10 +282,10 @@ class PolicyEvaluator:
                             ctypes.byref(self._out), ctypes.byref(self._trace_io), _ptr(env.obs), stream), name)
             return self.result
         if self._discrete:
-            _lib.check(self._lib.rr_policy_evaluate_discrete(env._h, _ptr(self._pack.pack()), self.policy.n_choices,
-                                                             self._table, self._pack.prec, self.n_episodes,
-                                                             self.max_steps, ctypes.byref(self._out), _ptr(env.obs),
-                                                             stream), "rr_policy_evaluate_discrete")
+            call, name = ((self._lib.rr_policy_evaluate_exact_discrete, "rr_policy_evaluate_exact_discrete")
+                          if self._exact else (self._lib.rr_policy_evaluate_discrete, "rr_policy_evaluate_discrete"))
+            _lib.check(call(env._h, _ptr(self._pack.pack()), self.policy.n_choices, self._table, self._pack.prec,
+                            self.n_episodes, self.max_steps, ctypes.byref(self._out), _ptr(env.obs), stream), name)
             return self.result
         call, name = ((self._lib.rr_policy_evaluate_exact, "rr_policy_evaluate_exact") if self._exact else
                       (self._lib.rr_policy_evaluate, "rr_policy_evaluate"))

@@ -36,6 +36,16 @@
   (b) `record_64`, the new call with 64 envs recorded, one per wave spread over the grid (env
   j * n / 64 + j); (c) `record_all`, every env recorded, with the bytes of rows it wrote; (d)
   `stepwise_64`, PolicyEvaluator(fused=False, record=) of the same 64 envs.
+
+    python tools/eval_bench.py --integrator dopri5 --policy categorical [--out profiles/eval_exact_discrete/eval_exact_discrete_bench.json]
+
+  the Categorical policy's one-launch exact evaluation (rr_policy_evaluate_exact_discrete) and its three
+  neighbours, all 3DOF, one episode per env from a fresh reset under TimeLimit `--tl`, four legs alternating
+  in one session as above (the one-launch legs in rotating order, then the step-by-step leg), `--reps` >= 5
+  timed runs each after a warm-up run: (1) `exact_discrete`, the new call with tests/discrete_ref.cat_policy(4, 1);
+  (2) `stepwise`, PolicyEvaluator(fused=False) with the same policy on a batch with the same seed;
+  (3) `exact_gaussian`, rr_policy_evaluate_exact with tests/rollout_ref.scaled_policy(7, 2, seed=5);
+  (4) `rk4_discrete`, rr_policy_evaluate_discrete on an RK4 batch with the policy of (1).
 """
 import argparse
 import json
@@ -68,6 +78,8 @@ def main():
     ap.add_argument("--integrator", choices=("rk4", "dopri5"), default="rk4")
     ap.add_argument("--tl", type=int, default=800, help="TimeLimit of the dopri5 leg")
     ap.add_argument("--record", action="store_true", help="the dopri5 leg's recording comparison")
+    ap.add_argument("--policy", choices=("gaussian", "categorical"), default="gaussian",
+                    help="categorical: the dopri5 leg's comparison of the Categorical policy's one-launch evaluation")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -93,6 +105,11 @@ def main():
             with open(args.out, "w") as f:
                 f.write(json.dumps(rec, indent=1) + "\n")
 
+    if args.policy == "categorical":
+        if args.integrator != "dopri5" or args.record:
+            raise SystemExit("--policy categorical goes with --integrator dopri5 and without --record")
+        write(exact_discrete_leg(args, rec, dev))
+        return
     if args.integrator == "dopri5":
         write(exact_trace_leg(args, rec, dev) if args.record else exact_leg(args, rec, dev))
         return
@@ -262,6 +279,61 @@ def exact_trace_leg(args, rec, dev):
         x["median_over_plain_max_us"] = x["us_median"] - a["us_max"]
         x["exceeds_plain_max_by_more_than_its_spread"] = bool(x["us_median"] - a["us_max"] > spread)
     rec["stepwise_over_record_64"] = rec["stepwise_64"]["us_median"] / rec["record_64"]["us_median"]
+    return rec
+
+
+def exact_discrete_leg(args, rec, dev):
+    """The --integrator dopri5 --policy categorical record (see the module docstring)."""
+    import torch
+    from rl_rocket_amd.batch import RocketBatch
+    from rl_rocket_amd.rollout import PolicyEvaluator
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from discrete_ref import cat_policy
+    from rollout_ref import scaled_policy
+
+    n, tl = args.n, args.tl
+    if args.reps < 5:
+        raise SystemExit("--policy categorical needs --reps >= 5")
+    cat = cat_policy(4, 1).to(dev)
+    gauss = scaled_policy(7, 2, seed=5, head_scale=1.0).to(dev)
+    rec.update(model="3DOF", integrator="dopri5 (rk4_discrete: rk4)", max_episode_steps=tl, n_episodes=1, reps=args.reps,
+               policy="tests/discrete_ref.cat_policy(4, 1); exact_gaussian: tests/rollout_ref.scaled_policy(7, 2, "
+               "seed=5, head_scale=1.0)")
+    legs = {}
+    for name, pol, integ, fused in (("exact_discrete", cat, "dopri5", True), ("exact_gaussian", gauss, "dopri5", True),
+                                    ("rk4_discrete", cat, "rk4", True), ("stepwise", cat, "dopri5", False)):
+        b = RocketBatch(n, model=3, device=dev, max_episode_steps=tl, integrator=integ, seed=1234)
+        e = PolicyEvaluator(b, pol, n_episodes=1, fused=fused)
+        assert e.fused == fused
+        legs[name] = (b, e, [])
+    one = ["exact_discrete", "exact_gaussian", "rk4_discrete"]
+    for r in range(args.reps + 1):  # run 0 is the warm-up; the legs alternate, each from the same reset
+        # the one-launch legs rotate, so that each of them follows the long step-by-step leg in turn
+        order = one[r % 3:] + one[:r % 3] + ["stepwise"]
+        for pos, name in enumerate(order):
+            b, e, runs = legs[name]
+            b.reset()
+            torch.cuda.synchronize()
+            us = timed(e.run, 1)
+            ln = e.result.ep_length[0].long()
+            waves = torch.nn.functional.pad(ln, (0, (-n) % 64)).view(-1, 64).max(dim=1).values
+            s = e.result.stats()
+            if r:
+                runs.append({"us": us, "position_in_round": pos, "env_steps": int(ln.sum()),
+                             "wave_steps": int(waves.sum()), "wave_steps_max": int(waves.max()),
+                             "env_steps_per_s": float(ln.sum()) / (us * 1e-6), "mean_ep_length": s["mean_ep_length"],
+                             "mean_reward": s["mean_reward"], "episodes": s["episodes"], "unfinished": s["unfinished"]})
+    for name, (b, e, runs) in legs.items():
+        us = [x["us"] for x in runs]
+        rec[name] = {"runs": runs, "us_median": statistics.median(us), "us_min": min(us), "us_max": max(us)}
+        b.close()
+    x = rec["exact_discrete"]
+    rec["stepwise_over_exact_discrete"] = rec["stepwise"]["us_median"] / x["us_median"]
+    rec["stepwise_min_over_exact_discrete_max"] = rec["stepwise"]["us_min"] / x["us_max"]
+    rec["exact_discrete_over_exact_gaussian"] = x["us_median"] / rec["exact_gaussian"]["us_median"]
+    rec["exact_discrete_over_rk4_discrete"] = x["us_median"] / rec["rk4_discrete"]["us_median"]
+    rec["gate_10x"] = bool(rec["stepwise_over_exact_discrete"] >= 10.0)
     return rec
 
 
