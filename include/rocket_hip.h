@@ -954,6 +954,42 @@ int rr_policy_evaluate_exact_discrete(rr_env* e, const float* params, int n_choi
                                       int precision, int n_episodes, int64_t max_steps, const rr_eval_out* out,
                                       float* obs, void* stream);
 
+/* ---- Sampled-action evaluation in ONE launch (pure additions to ABI 14: two new symbols, nothing
+ * existing changes) ----
+ * Replaces stable_baselines3 evaluate_policy(model, env, deterministic=False): whole episodes of the
+ * STOCHASTIC policy, the one PPO optimises, for every env of the handle at once.
+ * rr_policy_evaluate_sampled is rr_policy_evaluate (trace NULL) or rr_policy_evaluate_trace (trace given),
+ * and rr_policy_evaluate_discrete_sampled is rr_policy_evaluate_discrete or
+ * rr_policy_evaluate_discrete_trace, in every respect but the action: the rr_eval_out rows, the max_steps
+ * rule, the state the handle is left in, the untouched done list, the trace layout with its t < steps
+ * rule, obs, asynchrony, capture, no allocation.
+ * The action of step k of the call (k = 0, 1, ...: the loop index, whatever the env's elapsed field is)
+ * is the one rr_rollout_step(..., seed, iter, t = k, ...) / rr_rollout_step_discrete draws: the key from
+ * splitmix64(seed), the env's global id (env_id_offset + i), *iter (read once at kernel entry) and t = k;
+ *   Gaussian:     act = mean + exp(log_std) * eps (Box-Muller), the env steps with clip(act, -1, 1);
+ *   Categorical:  softmax over the first n_choices of the four logits, u = (mix32(key) >> 8) * 2^-24, the
+ *                 inverse-CDF index, the env steps with table[index] (not clipped).
+ * No value tower and no log-prob. An env's draws depend on nothing but its own global id, so shards with
+ * env_id_offset draw what the unsharded handle draws; an env that has finished n_episodes draws nothing
+ * any more (its column of the MFMAs is computed and dropped). An episode is therefore bit for bit the one
+ * rr_rollout_step / rr_rollout_step_discrete runs with the same (seed, *iter) and t counted from the call
+ * (tests/test_gpu_eval_sampled.py). The caller advances *iter between calls (as between collects) for
+ * fresh noise.
+ * Recorded (trace given): action[s][k][t][:] is the CLIPPED sample the env stepped with (the unclipped
+ * sample is not recorded), for the Categorical call the table row; choice (or NULL; needs trace) receives
+ * the sampled index.
+ * RR_EINVAL before any launch: everything the deterministic twin refuses (RR_INT_DOPRI5 handles, for the
+ * Categorical call a 6DOF handle and a precision other than RR_POLICY_FP32, ...), iter NULL, an effective
+ * max_steps (given, or n_episodes * max_episode_steps) above 2^31 - 1 (t is an int in rr_rollout_step),
+ * choice given without trace. */
+int rr_policy_evaluate_sampled(rr_env* e, const float* params, int precision, uint64_t seed, const uint64_t* iter,
+                               int n_episodes, int64_t max_steps, const rr_eval_out* out,
+                               const rr_eval_trace* trace /* or NULL */, float* obs, void* stream);
+int rr_policy_evaluate_discrete_sampled(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                                        uint64_t seed, const uint64_t* iter, int n_episodes, int64_t max_steps,
+                                        const rr_eval_out* out, const rr_eval_trace* trace /* or NULL */,
+                                        int32_t* choice /* or NULL; needs trace */, float* obs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

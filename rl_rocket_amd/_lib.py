@@ -262,6 +262,14 @@ SIGNATURES = {
     # rr_policy_evaluate_discrete's arguments, for an RR_INT_DOPRI5 handle
     "rr_policy_evaluate_exact_discrete": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int,
                                                          ctypes.c_int64, ctypes.POINTER(RrEvalOut), _P, _P]),
+    # rr_policy_evaluate_trace's / rr_policy_evaluate_discrete_trace's arguments with (seed, iter) after the
+    # precision; the trace may be None (the plain call)
+    "rr_policy_evaluate_sampled": (ctypes.c_int, [_P, _P, ctypes.c_int, ctypes.c_uint64, _P, ctypes.c_int,
+                                                  ctypes.c_int64, ctypes.POINTER(RrEvalOut),
+                                                  ctypes.POINTER(RrEvalTrace), _P, _P]),
+    "rr_policy_evaluate_discrete_sampled": (ctypes.c_int, [_P, _P, ctypes.c_int, _P, ctypes.c_int, ctypes.c_uint64, _P,
+                                                           ctypes.c_int, ctypes.c_int64, ctypes.POINTER(RrEvalOut),
+                                                           ctypes.POINTER(RrEvalTrace), _P, _P, _P]),
 }
 
 _LIB = None

@@ -94,7 +94,9 @@ class Demonstrations:
         multiply by), so on an RK4 / Euler batch it is bitwise the observation the policy was given;
         ``acts`` is the recorded action, the clipped mean the env stepped with. A trace with a ``choice``
         plane (a Categorical policy's) gives ``acts`` [M, 1], the chosen indices as floats: what ``BCUpdate``
-        and ``bc_train`` take for an ``MlpCategoricalActorCritic``.
+        and ``bc_train`` take for an ``MlpCategoricalActorCritic``. A trace recorded with
+        ``PolicyEvaluator(deterministic=False)`` gives the clipped samples (the sampled indices): a teacher
+        that explores, over the states its noise reaches.
 
         Row order: slot-major (the order of ``record=``), then episode, then step. Episodes cut by
         ``max_steps`` (partial) and episodes longer than the recording capacity (clipped) are left

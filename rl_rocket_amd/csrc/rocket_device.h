@@ -1191,6 +1191,14 @@ struct DiscHead {
     float table[4][2];
 };
 static_assert(std::is_trivially_copyable_v<DiscHead>, "DiscHead crosses TUs by memcpy");
+// ... and the noise key of the sampled evaluations (eval_sampled/, eval_sampled_discrete/), beside the
+// evaluation's EnvLaunch / EvalIO: the words of splitmix64(seed), as RolloutIO carries them, and the device
+// iteration word the kernel reads once at entry
+struct EvalSample {
+    uint32_t seed_lo, seed_hi;
+    const uint64_t* iter;
+};
+static_assert(std::is_trivially_copyable_v<EvalSample>, "EvalSample crosses TUs by memcpy");
 static_assert(std::is_trivially_copyable_v<EvalExactLaunch>, "EvalExactLaunch crosses TUs by memcpy");
 static_assert(std::is_trivially_copyable_v<EnvLaunch>, "EnvLaunch crosses TUs by memcpy");
 static_assert(std::is_trivially_copyable_v<ExactLaunch>, "ExactLaunch crosses TUs by memcpy");
@@ -1250,4 +1258,13 @@ __attribute__((visibility("hidden"))) int rrc_launch_eval_discrete_trace(const v
                                                                          const void* head, const void* trace, void* choice);
 // discrete_opts/rocket_ppo_discrete_opts.hip: rr_ppo_update_discrete_opts's launches, a DiscreteOptsLaunch
 __attribute__((visibility("hidden"))) int rrc_launch_discrete_opts(const void* launch, void* stream);
+// eval_sampled/rocket_eval_sampled.hip: the one-launch evaluation under the sampled action; launch / io as
+// rrc_launch_eval, sample points to the caller's EvalSample, trace to its EvalTraceIO or is nullptr (plain)
+__attribute__((visibility("hidden"))) int rrc_launch_eval_sampled(const void* launch, const void* io, const void* sample,
+                                                                  const void* trace);
+// eval_sampled_discrete/rocket_eval_sampled_discrete.hip: the Categorical policy's; head / choice as
+// rrc_launch_eval_discrete_trace (choice only with a trace)
+__attribute__((visibility("hidden"))) int rrc_launch_eval_discrete_sampled(const void* launch, const void* io,
+                                                                           const void* head, const void* sample,
+                                                                           const void* trace, void* choice);
 }

@@ -19,6 +19,16 @@
 // choice, an int32 plane [n_slots][n_episodes][steps] or nullptr) select one more region, seen by no other
 // kernel: the head keeps the winner's index and the step's record stores it beside the action row, under
 // the action row's t < steps rule. tr0 must stay the argument after io (trace_args reads it at that offset).
+// RR_EVAL_SAMPLE defined (eval_sampled/rocket_eval_sampled.hip: eval_sampled_kernel and eval_sampled_trace_kernel;
+// eval_sampled_discrete/rocket_eval_sampled_discrete.hip: their Categorical twins; no other kernel defines it)
+// selects the regions that SAMPLE the action (SB3 evaluate_policy(deterministic=False)) where the others take
+// the most likely one: the load of *iter at kernel entry, the noise key of the step, and in place of the
+// clipped means the Gaussian sample, or inside RR_DISCRETE_HEAD in place of the argmax the softmax, the
+// uniform draw and the inverse-CDF index with its table row (ci is then the sampled index). These lines are
+// rocket_rollout_body.inc's sample regions, statement for statement, with t = the loop index k and without
+// the log-prob, so an episode has the bits of the one rr_rollout_step / rr_rollout_step_discrete runs with
+// the same (seed, *iter). They need three more arguments after every other one: seed_lo, seed_hi (uint32_t,
+// the words of splitmix64(seed)) and iter (const uint64_t*).
     constexpr int NS = Dims<MODEL>::NS, NA = Dims<MODEL>::NA, NT = Dims<MODEL>::NT, EV = Dims<MODEL>::EV;
     constexpr int EPW = rol::Shape<2>::kEPW, NWV = rol::Shape<2>::kWaves;
 #ifdef RR_DISCRETE_HEAD
@@ -61,6 +71,9 @@
     const HotParams H = load_hot<NS>(P);
     const CounterLayout CL(P);
     const int32_t n_ep = io.n_episodes;
+#ifdef RR_EVAL_SAMPLE
+    const uint64_t it = *iter;  // read once: the whole call draws under one iteration word
+#endif
     int32_t ep = 0;            // episodes this env has completed
     float m0 = y0[NS - 1];     // mass at the first state of the running episode
     bool v0_new = false;
@@ -101,13 +114,57 @@
         const bool active = valid && ep < n_ep;
         if (__ballot(active) == 0) break;
 
+#ifdef RR_EVAL_SAMPLE
+        // ---- sampled action: the pi tower's means or logits, then rollout_step_kernel's sample of step t = k ----
+#else
         // ---- deterministic action: the pi tower's means, clipped ----
+#endif
         normalize_obs<NS>(y0, H.inv_norm, o);
         float value, mean[NH], a_env[NA];
         typename pol::XOp<PREC>::T x[2][L::KP1];
         rol::regs_x<NS, NH, PREC>(o, x);
         rol::policy_forward<NS, NH, PREC, 2, false>(sp, x, lane, value, mean);
-#ifdef RR_DISCRETE_HEAD
+#ifdef RR_EVAL_SAMPLE
+        // sample: the key and arithmetic of policy_act_kernel (rocket_rollout_body.inc's lines)
+        const uint32_t t = (uint32_t)k;
+        uint32_t key = mix32((uint32_t)(P.id_off + i) ^ seed_lo);
+        key = mix32(key ^ (uint32_t)it ^ seed_hi);
+        key = mix32(key ^ (uint32_t)(it >> 32) ^ (t * 0x9E3779B9u));
+#endif
+#if defined(RR_DISCRETE_HEAD) && defined(RR_EVAL_SAMPLE)
+        // The Categorical head's sample: discrete_act_kernel's lines as rocket_rollout_body.inc has them, without
+        // the log-prob. Softmax over the first n_choices logits
+        float zm = mean[0];
+#pragma unroll
+        for (int q = 1; q < NH; ++q) zm = q < n_choices ? fmaxf(zm, mean[q]) : zm;
+        float ex[NH], sum = 0.0f;
+#pragma unroll
+        for (int q = 0; q < NH; ++q) {
+            ex[q] = q < n_choices ? expf(mean[q] - zm) : 0.0f;
+            sum += ex[q];
+        }
+        const float u = (float)(mix32(key) >> 8) * 0x1p-24f;  // one uniform per env, [0, 1)
+        // index = the number of q in 0 .. K - 2 whose running sum p_0 + .. + p_q is <= u
+        int index = 0;
+        float cdf = 0.0f;
+#pragma unroll
+        for (int q = 0; q < NH - 1; ++q) {
+            cdf += ex[q] / sum;
+            index += (q < n_choices - 1 && cdf <= u) ? 1 : 0;
+        }
+        // the table row by compares: no data-dependent address
+        a_env[0] = tab.v[0][0];
+        a_env[1] = tab.v[0][1];
+#pragma unroll
+        for (int q = 1; q < NH; ++q)
+            if (index == q) {
+                a_env[0] = tab.v[q][0];
+                a_env[1] = tab.v[q][1];
+            }
+#if RR_EVAL_TRACE
+        const int32_t ci = index;  // the sampled index, for the trace's choice plane
+#endif
+#elif defined(RR_DISCRETE_HEAD)
         // the most probable choice: the lowest q < n_choices with the largest logit (torch.argmax: on a tie
         // the lowest index; a zero-packed head >= n_choices never wins), then its table row by compares
         float zb = mean[0];
@@ -126,6 +183,20 @@
                 ci = q;
 #endif
             }
+#elif defined(RR_EVAL_SAMPLE)
+        float eps[NA];
+#pragma unroll
+        for (int a = 0; a < NA; a += 2) {
+            const float2 z = pol::normal2(key + (uint32_t)a * 0x632BE5ABu);
+            eps[a] = z.x;
+            if (a + 1 < NA) eps[a + 1] = z.y;
+        }
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+            const float ls = sp[L::LS + a];
+            const float act = mean[a] + __builtin_amdgcn_exp2f(ls * 1.44269504088896341f) * eps[a];
+            a_env[a] = fminf(1.0f, fmaxf(-1.0f, act));  // the env steps with the clipped sample
+        }
 #else
 #pragma unroll
         for (int a = 0; a < NA; ++a) a_env[a] = fminf(1.0f, fmaxf(-1.0f, mean[a]));

@@ -389,6 +389,8 @@ __attribute__((weak)) int rrc_launch_eval_discrete(const void*, const void*, con
 __attribute__((weak)) int rrc_launch_discrete_opts(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_collect_discrete_stats(const void*, const void*, const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval_discrete_trace(const void*, const void*, const void*, const void*, void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_eval_sampled(const void*, const void*, const void*, const void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_eval_discrete_sampled(const void*, const void*, const void*, const void*, const void*, void*) { return kNoUnit; }
 }
 
 namespace {
@@ -1587,10 +1589,12 @@ namespace {
 // refuse it; with `traced` it records as rr_policy_evaluate_trace does): the argument checks, the
 // kernel's EvalIO and the launch. `who` prefixes every message. `head`: the Categorical policy's calls
 // (rr_policy_evaluate_discrete and, traced, rr_policy_evaluate_discrete_trace with its `choice` plane; with
-// `exact` and not traced, rr_policy_evaluate_exact_discrete).
+// `exact` and not traced, rr_policy_evaluate_exact_discrete). `sample`: rr_policy_evaluate_sampled and
+// rr_policy_evaluate_discrete_sampled (never with `exact`), whose kernels draw the action under that key.
 int evaluate(rr_env* e, const char* who, const float* params, int precision, int n_episodes, int64_t max_steps,
              const rr_eval_out* out, bool traced, const rr_eval_trace* trace, float* obs, void* stream,
-             bool exact = false, const DiscHead* head = nullptr, int32_t* choice = nullptr)
+             bool exact = false, const DiscHead* head = nullptr, int32_t* choice = nullptr,
+             const EvalSample* sample = nullptr)
 {
     const std::string w = std::string(who) + ": ";
     if (!e) return fail(RR_EINVAL, w + "null handle");
@@ -1617,6 +1621,8 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
     if (n_episodes < 1) return fail(RR_EINVAL, w + "n_episodes must be at least 1");
     if (max_steps <= 0) max_steps = (int64_t)n_episodes * e->p.max_episode_steps;
     if (max_steps <= 0) return fail(RR_EINVAL, w + "an env without a TimeLimit needs max_steps > 0");
+    if (sample && max_steps > (int64_t)INT32_MAX)  // the key's t is rr_rollout_step's int
+        return fail(RR_EINVAL, w + "max_steps (given or n_episodes * max_episode_steps) must not exceed 2^31 - 1");
     DeviceGuard g(e->device);
     EvalIO io = {};
     io.params = params;
@@ -1645,7 +1651,11 @@ int evaluate(rr_env* e, const char* who, const float* params, int precision, int
         t.n_slots = trace->n_slots;
         t.steps = trace->steps;
     }
-    if (head && exact && !traced) {
+    if (sample && head) {  // rr_policy_evaluate_discrete_sampled (eval_sampled_discrete/), plain or recording
+        err = (hipError_t)rrc_launch_eval_discrete_sampled(&L, &io, head, sample, traced ? &t : nullptr, choice);
+    } else if (sample) {  // rr_policy_evaluate_sampled (eval_sampled/), plain or recording
+        err = (hipError_t)rrc_launch_eval_sampled(&L, &io, sample, traced ? &t : nullptr);
+    } else if (head && exact && !traced) {
         // rr_policy_evaluate_exact_discrete: eval_exact_discrete_kernel (eval_exact_discrete/), eval_exact_kernel's launch
         const EvalExactLaunch X = {e->p.model, prec, L.grid, e->d_xp, &b, e->state64, stream};
         err = (hipError_t)rrx_launch_eval_exact_discrete(&X, &io, head);
@@ -1695,6 +1705,19 @@ int rr_policy_evaluate_exact_trace(rr_env* e, const float* params, int precision
 {
     return evaluate(e, "rr_policy_evaluate_exact_trace", params, precision, n_episodes, max_steps, out, true, trace,
                     obs, stream, true);
+}
+
+int rr_policy_evaluate_sampled(rr_env* e, const float* params, int precision, uint64_t seed, const uint64_t* iter,
+                               int n_episodes, int64_t max_steps, const rr_eval_out* out, const rr_eval_trace* trace,
+                               float* obs, void* stream)
+{
+    const char* who = "rr_policy_evaluate_sampled";
+    if (!iter) return refuse(who, "iter must not be null");
+    EvalSample S = {};
+    act_seed_words(seed, S.seed_lo, S.seed_hi);  // as rr_rollout_step: the same noise key
+    S.iter = iter;
+    return evaluate(e, who, params, precision, n_episodes, max_steps, out, trace != nullptr, trace, obs, stream, false,
+                    nullptr, nullptr, &S);
 }
 
 int rr_gae(int64_t T, int64_t n, const float* rewards, const float* values, const float* starts,
@@ -2357,6 +2380,36 @@ int rr_policy_evaluate_discrete_trace(rr_env* e, const float* params, int n_choi
     if (((uintptr_t)choice & 3) != 0) return refuse(who, "choice must be 4-B aligned");
     if (const int rc = disc_handle_ok(who, e); rc != RR_OK) return rc;
     return evaluate(e, who, params, precision, n_episodes, max_steps, out, true, trace, obs, stream, false, &H, choice);
+}
+
+int rr_policy_evaluate_discrete_sampled(rr_env* e, const float* params, int n_choices, const float* table, int precision,
+                                        uint64_t seed, const uint64_t* iter, int n_episodes, int64_t max_steps,
+                                        const rr_eval_out* out, const rr_eval_trace* trace, int32_t* choice, float* obs,
+                                        void* stream)
+{
+    // rr_policy_evaluate_discrete's refusals, with a trace rr_policy_evaluate_discrete_trace's, and the key's; the
+    // arguments before the handle
+    const char* who = "rr_policy_evaluate_discrete_sampled";
+    DiscHead H;
+    if (const int rc = disc_head_args(who, params, n_choices, table, precision, H); rc != RR_OK) return rc;
+    if (!iter) return refuse(who, "iter must not be null");
+    if (!out || !out->episodes) return refuse(who, "params, out and out->episodes must not be null");
+    if (n_episodes < 1) return refuse(who, "n_episodes must be at least 1");
+    if (trace) {
+        if (!trace->slot || !trace->state || !trace->length)
+            return refuse(who, "trace->slot, trace->state and trace->length must not be null");
+        if (trace->n_slots < 1 || trace->steps < 1)
+            return refuse(who, "trace->n_slots and trace->steps must be at least 1");
+        if (((uintptr_t)choice & 3) != 0) return refuse(who, "choice must be 4-B aligned");
+    } else if (choice) {
+        return refuse(who, "choice needs trace (the indices are recorded beside the action rows)");
+    }
+    if (const int rc = disc_handle_ok(who, e); rc != RR_OK) return rc;
+    EvalSample S = {};
+    act_seed_words(seed, S.seed_lo, S.seed_hi);  // as rr_rollout_step_discrete: the same noise key
+    S.iter = iter;
+    return evaluate(e, who, params, precision, n_episodes, max_steps, out, trace != nullptr, trace, obs, stream, false,
+                    &H, choice, &S);
 }
 
 int rr_ppo_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes)

@@ -24,7 +24,9 @@ class EpisodeRecord:
     ``complete`` is False for an episode cut by ``max_steps`` (``partial=True``) or by the
     recording capacity (``clipped=True``); ``length`` is the number of steps the episode took.
     ``choices`` [L] (int32) are the indices of a Categorical policy's choices, whose table rows
-    ``actions`` holds; None for a Gaussian policy."""
+    ``actions`` holds; None for a Gaussian policy. Under ``PolicyEvaluator(deterministic=False)`` an action
+    row is the clipped SAMPLE the env stepped with (the unclipped sample is not recorded) and ``choices``
+    the sampled indices."""
 
     def __init__(self, cfg, states, actions, terms, rewards, env_id=None, episode=0, length=None, complete=True,
                  choices=None):

@@ -1,4 +1,5 @@
-"""Deterministic policy evaluation on the device (SB3 EvalCallback / evaluate_policy + EpisodeAnalyzer)."""
+"""Policy evaluation on the device (SB3 EvalCallback / evaluate_policy + EpisodeAnalyzer): under the most
+likely action or, with ``deterministic=False``, under the sampled one."""
 import torch
 
 from ._lib import (RR_EVAL_BOUNDS as EVAL_BOUNDS, RR_EVAL_EVENT as EVAL_EVENT, RR_EVAL_LANDED as EVAL_LANDED,
@@ -119,16 +120,51 @@ class PolicyEvaluator:
     step-by-step loop; the recorded action rows are the table rows the env stepped with, and
     ``EvalTrace.choice`` [K, ne, S] (int32) holds their indices, from which ``Demonstrations.from_trace``
     builds the ``[M, 1]`` index demonstrations of ``rr_bc_update_discrete``. A ``policy_dtype`` other than
-    "fp32" raises for it."""
+    "fp32" raises for it.
+
+    ``deterministic=False`` (default True: everything above, "the clipped mean action, always") evaluates
+    the STOCHASTIC policy, SB3's ``evaluate_policy(model, env, deterministic=False)``: the action of step
+    ``k`` of the call is the sample ``rr_rollout_step`` / ``rr_rollout_step_discrete`` draws at ``t = k``
+    under ``(seed, iter)`` (``mean + exp(log_std) * eps`` clipped to [-1, 1]; for a Categorical policy the
+    inverse-CDF index of one uniform draw and its table row), so an episode is bit for bit the one the
+    per-step rollout runs. ``run()`` is ONE launch (``rr_policy_evaluate_sampled``, for a Categorical policy
+    ``rr_policy_evaluate_discrete_sampled``), with ``record=`` the same launch recording; the recorded
+    action rows are then the CLIPPED samples the env stepped with (the table rows, ``choice`` the sampled
+    indices), never the unclipped sample. The evaluator owns ``self.seed`` (from ``seed``) and ``self.iter``,
+    an int64 ``[1]`` device tensor that ``run()`` advances by one in stream order, exactly as
+    ``DeviceRollout.iter``: a captured ``run()`` draws fresh noise at every replay, and two evaluators with
+    equal ``(seed, iter)`` on twin batches produce equal bits. A Gaussian policy resolves ``fused=None`` as
+    above and takes every ``policy_dtype``; a Categorical one needs ``fused=True`` and fp32. It raises
+    ``ValueError`` with ``fused=False``, a ``fused=None`` that resolves to the step-by-step path (a policy
+    that is not 64x64, an ``integrator="dopri5"`` batch), ``fused=True`` on a dopri5 batch, a CPU batch and
+    ``record_in_launch=True``: the step-by-step path and the exact integrator are out of scope for it."""
 
     def __init__(self, batch, policy, n_episodes=5, max_steps=None, policy_dtype="fp32", fused=None, record=None,
-                 record_steps=None, record_in_launch=None):
+                 record_steps=None, record_in_launch=None, deterministic=True, seed=0):
         from . import _lib
         from .params import STATE_NAMES_3DOF, STATE_NAMES_6DOF
 
         self.env, self.policy = batch, policy
         n, ns, na = batch.num_envs, batch.state_dim, batch.action_dim
         self._discrete = isinstance(policy, MlpCategoricalActorCritic)
+        self.deterministic = bool(deterministic)
+        if not self.deterministic:  # the refusals of the sampled evaluation: the batch's params and device only
+            scope = ("deterministic=False is the one-launch sampled evaluation (rr_policy_evaluate_sampled): the "
+                     "step-by-step path and the exact integrator are out of scope for it")
+            if record_in_launch:
+                raise ValueError("deterministic=False with record_in_launch=True is not available; " + scope)
+            if fused is not None and not fused:
+                raise ValueError("deterministic=False with fused=False is not available; " + scope)
+            if torch.device(batch.device).type != "cuda":
+                raise ValueError("deterministic=False needs a batch on a CUDA device; " + scope)
+            if int(batch.params.integrator) == _lib.RR_INT_DOPRI5:
+                raise ValueError("deterministic=False on an integrator=\"dopri5\" batch is not available; " + scope)
+            if self._discrete and not fused:
+                raise ValueError("deterministic=False for a Categorical policy needs fused=True, as its other "
+                                 "launches; " + scope)
+            if not self._discrete and not fused_grad_supported(policy, ns, na):
+                raise ValueError("deterministic=False needs an MlpActorCritic with 64x64 towers (this policy takes "
+                                 "the step-by-step path); " + scope)
         if record_in_launch:  # the refusals that need nothing of the batch but its integrator
             if record is None:
                 raise ValueError("record_in_launch=True needs record")
@@ -196,6 +232,9 @@ class PolicyEvaluator:
                                  self.final_state, STATE_NAMES_6DOF if batch.model == 6 else STATE_NAMES_3DOF,
                                  trace=self.trace)
         self._lib = _lib.load()
+        if not self.deterministic:  # the noise key of run(): advanced in stream order, as DeviceRollout.iter
+            self.seed = int(seed) & (2 ** 64 - 1)
+            self.iter = torch.zeros((1,), dtype=torch.int64, device=dev)
         if self.fused:
             self._pack = PolicyPack(policy, ns, policy.n_choices if self._discrete else na, dev, precision=policy_dtype)
             if self._discrete:  # the host table the call copies into its launch
@@ -269,6 +308,21 @@ class PolicyEvaluator:
 
         env = self.env
         stream = ctypes.c_void_p(torch.cuda.current_stream(env.device).cuda_stream)
+        if not self.deterministic:  # one launch of the sampled call, then the iteration word moves on
+            trace = ctypes.byref(self._trace_io) if self.trace is not None else None
+            if self._discrete:
+                _lib.check(self._lib.rr_policy_evaluate_discrete_sampled(
+                    env._h, _ptr(self._pack.pack()), self.policy.n_choices, self._table, self._pack.prec, self.seed,
+                    _ptr(self.iter), self.n_episodes, self.max_steps, ctypes.byref(self._out), trace,
+                    self._choice if self.trace is not None else None, _ptr(env.obs), stream),
+                    "rr_policy_evaluate_discrete_sampled")
+            else:
+                _lib.check(self._lib.rr_policy_evaluate_sampled(
+                    env._h, _ptr(self._pack.pack()), self._pack.prec, self.seed, _ptr(self.iter), self.n_episodes,
+                    self.max_steps, ctypes.byref(self._out), trace, _ptr(env.obs), stream),
+                    "rr_policy_evaluate_sampled")
+            self.iter.add_(1)
+            return self.result
         if self.trace is not None and self._discrete:
             _lib.check(self._lib.rr_policy_evaluate_discrete_trace(
                 env._h, _ptr(self._pack.pack()), self.policy.n_choices, self._table, self._pack.prec, self.n_episodes,
@@ -397,9 +451,11 @@ class PolicyEvaluator:
 
 
 def evaluate_policy(policy, batch, n_eval_episodes=5, return_episode_rewards=False, **kw):
-    """SB3 ``evaluate_policy(model, env, n_eval_episodes, deterministic=True)`` on a ``RocketBatch``:
+    """SB3 ``evaluate_policy(model, env, n_eval_episodes, deterministic=True)`` on a ``RocketBatch``, or with
+    ``deterministic=False, seed=...`` SB3's ``evaluate_policy(..., deterministic=False)`` (the sampled actions
+    of ``PolicyEvaluator(deterministic=False)``, one launch):
     resets every env, runs a ``PolicyEvaluator`` (``**kw``: max_steps, policy_dtype, fused, record,
-    record_in_launch, ...) and returns ``(mean_reward, std_reward)`` or, with ``return_episode_rewards``, ``(episode_rewards,
+    record_in_launch, deterministic, seed, ...) and returns ``(mean_reward, std_reward)`` or, with ``return_episode_rewards``, ``(episode_rewards,
     episode_lengths)`` as lists over the finished episodes.
 
     ``n_eval_episodes`` is PER ENV here: every env runs that many episodes, N * n_eval_episodes in

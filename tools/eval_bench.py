@@ -46,6 +46,19 @@
   (2) `stepwise`, PolicyEvaluator(fused=False) with the same policy on a batch with the same seed;
   (3) `exact_gaussian`, rr_policy_evaluate_exact with tests/rollout_ref.scaled_policy(7, 2, seed=5);
   (4) `rk4_discrete`, rr_policy_evaluate_discrete on an RK4 batch with the policy of (1).
+
+    python tools/eval_bench.py --sampled [--reps 7] [--out profiles/eval_sampled/eval_sampled_bench.json]
+
+  the sampled-action evaluation (rr_policy_evaluate_sampled, PolicyEvaluator(deterministic=False)), 6DOF, fp32,
+  RK4, tests/rollout_ref.scaled_policy(14, 3, seed=5, head_scale=1.0) at log_std = -1, `--reps` >= 7 samples of
+  every leg, the legs alternating in rotating order in one process, medians with min .. max.
+  `per_step`: n_episodes = max_steps = 64 under TimeLimit 800 (no env ends 64 episodes in 64 steps, so every env
+  steps 64 times in every call), the sampled call beside rr_policy_evaluate and beside a 64-step
+  rr_rollout_collect with the same (seed, iter) on twin batches; a sample is a block of `--calls` calls, in us
+  per call and per step. The collect and the sampled evaluation draw the same noise, so their batches must end
+  in the same state (`same_state_as_collect`). `whole`: one episode per env from a fresh reset, sampled beside
+  deterministic, and sampled with 64 envs recorded (one per wave spread over the grid) and with every env
+  recorded; a sample is one call.
 """
 import argparse
 import json
@@ -80,6 +93,7 @@ def main():
     ap.add_argument("--record", action="store_true", help="the dopri5 leg's recording comparison")
     ap.add_argument("--policy", choices=("gaussian", "categorical"), default="gaussian",
                     help="categorical: the dopri5 leg's comparison of the Categorical policy's one-launch evaluation")
+    ap.add_argument("--sampled", action="store_true", help="the sampled-action evaluation's comparison (RK4)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -105,6 +119,11 @@ def main():
             with open(args.out, "w") as f:
                 f.write(json.dumps(rec, indent=1) + "\n")
 
+    if args.sampled:
+        if args.integrator != "rk4" or args.record or args.policy != "gaussian":
+            raise SystemExit("--sampled goes alone")
+        write(sampled_leg(args, rec, dev))
+        return
     if args.policy == "categorical":
         if args.integrator != "dopri5" or args.record:
             raise SystemExit("--policy categorical goes with --integrator dopri5 and without --record")
@@ -334,6 +353,103 @@ def exact_discrete_leg(args, rec, dev):
     rec["exact_discrete_over_exact_gaussian"] = x["us_median"] / rec["exact_gaussian"]["us_median"]
     rec["exact_discrete_over_rk4_discrete"] = x["us_median"] / rec["rk4_discrete"]["us_median"]
     rec["gate_10x"] = bool(rec["stepwise_over_exact_discrete"] >= 10.0)
+    return rec
+
+
+def sampled_leg(args, rec, dev, k=64):
+    """The --sampled record (see the module docstring)."""
+    import torch
+    from rl_rocket_amd.batch import RocketBatch
+    from rl_rocket_amd.params import ENV_CONFIG_6DOF
+    from rl_rocket_amd.rollout import DeviceRollout, PolicyEvaluator
+
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    from rollout_ref import scaled_policy
+
+    n, reps = args.n, max(args.reps, 7)
+    if n % 64:
+        raise SystemExit("--sampled needs n a multiple of 64")
+    pol = scaled_policy(14, 3, seed=5, head_scale=1.0)
+    with torch.no_grad():
+        pol.log_std.fill_(-1.0)
+    pol = pol.to(dev)
+    rec.update(integrator="rk4", policy="tests/rollout_ref.scaled_policy(14, 3, seed=5, head_scale=1.0), log_std = -1",
+               reps=reps, seed=11)
+
+    def env():
+        b = RocketBatch(n, model=6, device=dev, max_episode_steps=800, **dict(ENV_CONFIG_6DOF, seed=1234))
+        b.reset()
+        return b
+
+    def summary(us):
+        return {"us": us, "us_median": statistics.median(us), "us_min": min(us), "us_max": max(us)}
+
+    # ---- (a) the cost of a step: k steps of every env in every call ----
+    ro = DeviceRollout(env(), pol, n_steps=k, policy_dtype="fp32", seed=11)
+    legs = {"collect": (ro.env, ro.collect),
+            "sampled": None, "deterministic": None}
+    start = ro.env.checkpoint()  # (DeviceRollout reset its batch once more: the twins start where it starts)
+    for name, kw in (("sampled", dict(deterministic=False, seed=11)), ("deterministic", {})):
+        b = env()
+        b.restore(start)
+        legs[name] = (b, PolicyEvaluator(b, pol, n_episodes=k, max_steps=k, **kw).run)
+    order = list(legs)
+    for _ in range(10):  # warm-up: code objects loaded, episodes spread over their lengths
+        for name in order:
+            legs[name][1]()
+    torch.cuda.synchronize()
+    t = {name: [] for name in order}
+    for r in range(reps):
+        for name in order[r % 3:] + order[:r % 3]:
+            t[name].append(timed(legs[name][1], args.calls))
+    same = all(torch.equal(x, y) for x, y in zip(legs["collect"][0].get_state(), legs["sampled"][0].get_state()))
+    per = {"steps": k, "calls_per_sample": args.calls, "same_state_as_collect": bool(same)}
+    for name in order:
+        per[name] = summary(t[name])
+        per[name]["us_per_step_median"] = per[name]["us_median"] / k
+        legs[name][0].close()
+    per["sampled_below_collect"] = bool(per["sampled"]["us_median"] < per["collect"]["us_median"])
+    per["sampled_max_below_collect_min"] = bool(per["sampled"]["us_max"] < per["collect"]["us_min"])
+    per["sampled_over_deterministic"] = per["sampled"]["us_median"] / per["deterministic"]["us_median"]
+    per["sampled_over_collect"] = per["sampled"]["us_median"] / per["collect"]["us_median"]
+    rec["per_step"] = per
+
+    # ---- (b) whole evaluations: one episode per env from a fresh reset ----
+    ids64 = [j * (n // 64) + j for j in range(64)]  # lane j of every (n / 4096)-th wave
+    rec["recorded_64"] = ids64
+    sam = dict(deterministic=False, seed=11)
+    whole = {}
+    for name, kw in (("deterministic", {}), ("sampled", sam), ("sampled_record_64", dict(sam, record=ids64)),
+                     ("sampled_record_all", dict(sam, record=torch.arange(n)))):
+        b = env()
+        whole[name] = (b, PolicyEvaluator(b, pol, n_episodes=1, **kw), [])
+    order = list(whole)
+    for r in range(reps + 1):  # run 0 is the warm-up; the legs alternate in rotating order
+        for name in order[r % 4:] + order[:r % 4]:
+            b, e, runs = whole[name]
+            b.reset()
+            torch.cuda.synchronize()
+            us = timed(e.run, 1)
+            ln = e.result.ep_length[0].long()
+            waves = ln.view(-1, 64).max(dim=1).values
+            row = {"us": us, "env_steps": int(ln.sum()), "wave_steps": int(waves.sum()), "wave_steps_max": int(waves.max()),
+                   "unfinished": int((e.result.episodes < 1).sum())}
+            if e.trace is not None:  # rows written: length + 1 state rows, length action and terms rows, the length word
+                tr = e.trace
+                L = tr.length[0].long().clamp(max=tr.steps)
+                per_row = 4 * (tr.state.shape[-1] + tr.action.shape[-1] + tr.terms.shape[-1])
+                row["trace_bytes"] = int(L.sum()) * per_row + L.numel() * (4 * tr.state.shape[-1] + 4)
+            if r:
+                runs.append(row)
+    out = {}
+    for name, (b, e, runs) in whole.items():
+        out[name] = dict(summary([x["us"] for x in runs]), runs=runs,
+                         us_per_wave_step_of_longest_wave=statistics.median(x["us"] / x["wave_steps_max"] for x in runs))
+        b.close()
+    out["sampled_over_deterministic"] = out["sampled"]["us_median"] / out["deterministic"]["us_median"]
+    for name in ("sampled_record_64", "sampled_record_all"):
+        out[name]["over_sampled_median_us"] = out[name]["us_median"] - out["sampled"]["us_median"]
+    rec["whole"] = out
     return rec
 
 
