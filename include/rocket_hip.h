@@ -736,6 +736,46 @@ int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* g
                  double beta1, double beta2, float eps, float* stats, uint32_t flags,
                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* One A2C update on a device rollout, rows idx[0 .. batch): stable_baselines3 A2C.train() for the
+ * MlpPolicy actor-critic with a diagonal Gaussian, loss.backward(), clip_grad_norm_ and the optimizer's
+ * step:
+ *   A    = advantages[idx], or with normalize_advantage != 0 (A - mean(A)) / (std(A) + 1e-8)
+ *   policy_loss = -mean(A log_prob(actions)),   value_loss = mean((returns - V)^2)
+ *   entropy     = sum_a (0.5 + 0.5 log 2 pi + log_std_a)
+ *   loss        = policy_loss - ent_coef entropy + vf_coef value_loss
+ * There is no probability ratio: the rollout's stored log-probs are not an argument. Arrays, pointer
+ * conventions and the 13 tensors' order are rr_ppo_update's. `optimizer` chooses the step, on the
+ * optimizer's own state tensors:
+ *   RR_A2C_RMSPROP     torch.optim.RMSprop      sq = alpha sq + (1 - alpha) g g; p -= lr g / (sqrt(sq) + eps)
+ *   RR_A2C_RMSPROP_TF  SB3's RMSpropTFLike      the same sq;                    p -= lr g / sqrt(sq + eps)
+ *   RR_A2C_ADAM        torch.optim.Adam(capturable=True), rr_ppo_update's step (use_rms_prop=False)
+ * square_avg holds RMSprop's square_avg tensors or Adam's exp_avg_sq; exp_avg is Adam's and NULL
+ * otherwise; alpha_or_beta1 is RMSprop's alpha or Adam's beta1, beta2 is Adam's only. No momentum, not
+ * centered, no weight decay. max_grad_norm 0 is no clip; the clipped gradients are left in grads, and
+ * every step tensor (a device float each) counts the call. lr is a device float.
+ * stats is a device block of RR_A2C_STAT_SLOTS floats or NULL: [policy_loss, value_loss, entropy, loss,
+ * mean log_prob, 0, 0, 0]. One call is four launches (advantage sums and packing, gradient, finish,
+ * optimizer). Capturable in a graph; deterministic (fixed-order sums, no atomics). RR_EINVAL before any
+ * launch for unsupported dimensions, batch < 2, a null argument or tensor, an unknown optimizer, NaN,
+ * infinite or negative ent_coef / vf_coef / max_grad_norm / eps, alpha_or_beta1 or beta2 outside [0, 1),
+ * a workspace too small or not 16-B aligned. workspace: rr_a2c_update_workspace_size bytes. */
+enum { RR_A2C_RMSPROP = 0, RR_A2C_RMSPROP_TF = 1, RR_A2C_ADAM = 2 };
+enum {
+    RR_A2C_STAT_POLICY_LOSS = 0,
+    RR_A2C_STAT_VALUE_LOSS,
+    RR_A2C_STAT_ENTROPY,
+    RR_A2C_STAT_LOSS,
+    RR_A2C_STAT_LOG_PROB,      /* mean log_prob(actions) */
+    RR_A2C_STAT_SLOTS = 8      /* floats */
+};
+int rr_a2c_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes);
+int rr_a2c_update(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* square_avg,
+                  float* const* exp_avg, float* const* step, const float* obs, const float* actions,
+                  const float* advantages, const float* returns, const int64_t* idx, int64_t batch,
+                  int normalize_advantage, float ent_coef, float vf_coef, float max_grad_norm, int optimizer,
+                  const float* lr, double alpha_or_beta1, double beta2, float eps, float* stats,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Discrete 3DOF actions: the Categorical policy --------------------------------------------------
  * The reference's DiscreteActions3DOF (wrappers.py:24-35) turns the 3DOF env's [gimbal, thrust]
  * action into Discrete(K) through a table of K rows; behind it SB3 builds an MlpPolicy with the same

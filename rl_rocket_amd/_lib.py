@@ -134,6 +134,11 @@ RR_BC_CHAINED = 0x1
 (RR_BC_STAT_NEGLOGP, RR_BC_STAT_ENTROPY, RR_BC_STAT_ENT_LOSS, RR_BC_STAT_PROB_TRUE_ACT, RR_BC_STAT_L2_NORM,
  RR_BC_STAT_L2_LOSS, RR_BC_STAT_LOSS) = range(7)
 RR_BC_STAT_SLOTS = 8
+# rr_a2c_update's optimizers and the slots of its statistics block (rocket_hip.h RR_A2C_*): 8 floats
+RR_A2C_RMSPROP, RR_A2C_RMSPROP_TF, RR_A2C_ADAM = range(3)
+(RR_A2C_STAT_POLICY_LOSS, RR_A2C_STAT_VALUE_LOSS, RR_A2C_STAT_ENTROPY, RR_A2C_STAT_LOSS,
+ RR_A2C_STAT_LOG_PROB) = range(5)
+RR_A2C_STAT_SLOTS = 8
 
 
 class RrEvalTrace(ctypes.Structure):
@@ -224,6 +229,10 @@ SIGNATURES = {
     "rr_bc_update": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 8 +
                      [ctypes.c_int64, ctypes.c_float, ctypes.c_float, _P, ctypes.c_double, ctypes.c_double,
                       ctypes.c_float, _P, ctypes.c_uint32, _P, ctypes.c_int64, _P]),
+    "rr_a2c_update_workspace_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P]),
+    "rr_a2c_update": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 10 +
+                      [ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, _P,
+                       ctypes.c_double, ctypes.c_double, ctypes.c_float, _P, _P, ctypes.c_int64, _P]),
     "rr_policy_layout_discrete": (ctypes.c_int, [ctypes.c_int, _P]),
     "rr_policy_pack_discrete": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, _P, _P]),
     "rr_policy_act_discrete": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int64,

@@ -80,6 +80,11 @@ SRC_EVAL_EXACT_DISCRETE = os.path.join(HERE, "csrc", "eval_exact_discrete", "roc
 # collect's settings
 SRC_EVAL_SAMPLED = os.path.join(HERE, "csrc", "eval_sampled", "rocket_eval_sampled.hip")
 SRC_EVAL_SAMPLED_DISCRETE = os.path.join(HERE, "csrc", "eval_sampled_discrete", "rocket_eval_sampled_discrete.hip")
+# SB3's A2C on the device (rr_a2c_update): the learner's towers with the A2C head derivative, its prep and
+# finish bodies and an RMSprop body of its own (the .inc beside the unit), in a module of its own for the
+# same reason, with the learner's settings
+SRC_A2C = os.path.join(HERE, "csrc", "a2c", "rocket_a2c.hip")
+INC_A2C_RMSPROP = os.path.join(HERE, "csrc", "a2c", "rocket_rmsprop_body.inc")
 HEADER = os.path.join(ROOT, "include", "rocket_hip.h")
 OUT = os.path.join(HERE, "librocket_hip.so")
 # benchmark-only helper (not part of the product ABI): bench.py's event-timed direct-launch region
@@ -115,19 +120,20 @@ def command(resource_usage=False, out=OUT, defines=(), extra=(), src=SRC, compil
 
 
 def sources():
-    """Every file the eighteen translation units are compiled from: all of csrc/ (three units and the
+    """Every file the nineteen translation units are compiled from: all of csrc/ (three units and the
     text the others include, the behaviour-cloning kernels' rocket_bc.inc among it), the recording and
     the exact-mode evaluation's units, the statistics collect's unit with the .inc beside it, the
     learner-options, behaviour-cloning, discrete-action, discrete behaviour-cloning, discrete-rollout,
     discrete learner-options, discrete statistics-collect, discrete recording-evaluation, recording
-    exact-evaluation, discrete exact-evaluation and the two sampled-evaluation units and the C-ABI header, sorted (tests/test_build_sources.py checks that the
+    exact-evaluation, discrete exact-evaluation, the two sampled-evaluation and the A2C units (the latter with the .inc beside it)
+    and the C-ABI header, sorted (tests/test_build_sources.py checks that the
     #include graph stays inside this list)."""
     csrc = os.path.join(HERE, "csrc")
     return sorted([os.path.join(csrc, f) for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f))]
                   + [SRC_EVAL_TRACE, SRC_EVAL_EXACT, SRC_COLLECT_STATS, INC_COLLECT_STATS, SRC_PPO_OPTS, SRC_BC, SRC_DISCRETE,
                      SRC_BC_DISCRETE, SRC_ROLLOUT_DISCRETE, SRC_DISCRETE_OPTS, SRC_COLLECT_STATS_DISCRETE,
                      SRC_EVAL_TRACE_DISCRETE, SRC_EVAL_EXACT_TRACE, SRC_EVAL_EXACT_DISCRETE, SRC_EVAL_SAMPLED,
-                     SRC_EVAL_SAMPLED_DISCRETE, HEADER])
+                     SRC_EVAL_SAMPLED_DISCRETE, SRC_A2C, INC_A2C_RMSPROP, HEADER])
 
 
 def source_hash():
@@ -146,12 +152,12 @@ def source_hash():
 
 
 def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
-    """The six hipcc calls that build the library's eighteen translation units: the main, exact-mode,
+    """The six hipcc calls that build the library's nineteen translation units: the main, exact-mode,
     collect, recording-evaluation and exact-evaluation units compiled to objects (the latter four with EXACT_FLAGS /
     COLLECT_FLAGS / COLLECT_FLAGS / EVAL_EXACT_FLAGS); the last step compiles the learner-options, the
     behaviour-cloning, the discrete-action, the discrete behaviour-cloning, the discrete-rollout, the discrete
     learner-options, the discrete statistics-collect, the discrete recording-evaluation, the recording exact-evaluation, the
-    discrete exact-evaluation, the two sampled-evaluation and the statistics collect's units
+    discrete exact-evaluation, the two sampled-evaluation, the A2C and the statistics collect's units
     (all COLLECT_FLAGS, each a module of its own) and links them with
     those objects into `out` in one hipcc call. The flags of that call reach only the sources it
     compiles: the objects already hold their code objects."""
@@ -174,14 +180,15 @@ def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
                                                                             SRC_EVAL_EXACT_TRACE,
                                                                             SRC_EVAL_EXACT_DISCRETE,
                                                                             SRC_EVAL_SAMPLED,
-                                                                            SRC_EVAL_SAMPLED_DISCRETE],
+                                                                            SRC_EVAL_SAMPLED_DISCRETE,
+                                                                            SRC_A2C],
                  SRC_COLLECT_STATS,
                  preload=preload)
     return [c1, c2, c3, c4, c5, c6]
 
 
 def build_lib(out=OUT, defines=(), extra=(), resource_usage=False, verbose=True, preload=4):
-    """Compile five translation units to objects (in parallel), then the other thirteen in the call that
+    """Compile five translation units to objects (in parallel), then the other fourteen in the call that
     links `out`."""
     cmds = commands(resource_usage, out, defines, extra, preload=preload)
     if verbose:

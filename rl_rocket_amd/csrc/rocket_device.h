@@ -1243,6 +1243,8 @@ __attribute__((visibility("hidden"))) int rrc_launch_bc(const void* launch, void
 __attribute__((visibility("hidden"))) int rrc_launch_discrete(const void* launch, void* stream);
 // bc_discrete/rocket_bc_discrete.hip: rr_bc_update_discrete's launches, a BcLaunch with n_choices and a sink
 __attribute__((visibility("hidden"))) int rrc_launch_bc_discrete(const void* launch, void* stream);
+// a2c/rocket_a2c.hip: rr_a2c_update's launches, an A2cLaunch
+__attribute__((visibility("hidden"))) int rrc_launch_a2c(const void* launch, void* stream);
 // rollout_discrete/rocket_rollout_discrete.hip: the Categorical policy's one-launch collect (multi != 0),
 // its per-step launch and its one-launch evaluation; head points to the caller's DiscHead
 __attribute__((visibility("hidden"))) int rrc_launch_rollout_discrete(const void* launch, const void* io, const void* head,

@@ -384,6 +384,7 @@ __attribute__((weak)) int rrc_launch_learner_opts(const void*, void*) { return k
 __attribute__((weak)) int rrc_launch_bc(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_discrete(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_bc_discrete(const void*, void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_a2c(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_rollout_discrete(const void*, const void*, const void*, int) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval_discrete(const void*, const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_discrete_opts(const void*, void*) { return kNoUnit; }
@@ -2131,6 +2132,79 @@ int rr_bc_update(int obs_dim, int act_dim, float* const* params, float* const* g
     if (rc != RR_OK) return rc;
     const hipError_t err = (hipError_t)rrc_launch_bc(&L, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_bc_update: launch");
+}
+
+// ---- A2C (a2c/rocket_a2c.hip): the workspace is rr_ppo_update's (ppo_carve's sections and the finish's sums) ----
+int rr_a2c_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_t* bytes)
+{
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
+    const int rc = learner_shape_ok("rr_a2c_update_workspace_size", sh, batch, bytes);
+    if (rc == RR_OK) *bytes = ppo_update_bytes(sh, batch);
+    return rc;
+}
+
+int rr_a2c_update(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* square_avg,
+                  float* const* exp_avg, float* const* step, const float* obs, const float* actions,
+                  const float* advantages, const float* returns, const int64_t* idx, int64_t batch,
+                  int normalize_advantage, float ent_coef, float vf_coef, float max_grad_norm, int optimizer,
+                  const float* lr, double alpha_or_beta1, double beta2, float eps, float* stats,
+                  void* workspace, int64_t workspace_bytes, void* stream)
+{
+    const char* who = "rr_a2c_update";
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
+    if (const int rc = learner_shape_ok(who, sh, batch, nullptr, false); rc != RR_OK) return rc;
+    if (optimizer != RR_A2C_RMSPROP && optimizer != RR_A2C_RMSPROP_TF && optimizer != RR_A2C_ADAM)
+        return refuse(who, "optimizer must be RR_A2C_RMSPROP, RR_A2C_RMSPROP_TF or RR_A2C_ADAM");
+    const bool adam = optimizer == RR_A2C_ADAM;
+    if (!params || !grads || !square_avg || (adam && !exp_avg) || !step || !obs || !actions || !advantages || !returns ||
+        !idx || !lr)
+        return refuse(who, "null argument");
+    if (const int rc = learner_ws_ok(who, workspace, workspace_bytes, ppo_update_bytes(sh, batch), 0, 0); rc != RR_OK)
+        return rc;
+    // NaN fails every comparison: !(x >= 0 && x < inf) is true for NaN, negatives and infinities
+    if (!(ent_coef >= 0.0f && ent_coef < HUGE_VALF)) return refuse(who, "ent_coef must be finite and >= 0");
+    if (!(vf_coef >= 0.0f && vf_coef < HUGE_VALF)) return refuse(who, "vf_coef must be finite and >= 0");
+    if (!(max_grad_norm >= 0.0f && max_grad_norm < HUGE_VALF))
+        return refuse(who, "max_grad_norm must be finite and >= 0 (0: no clip)");
+    if (!(eps >= 0.0f && eps < HUGE_VALF)) return refuse(who, "eps must be finite and >= 0");
+    if (!(alpha_or_beta1 >= 0.0 && alpha_or_beta1 < 1.0))
+        return refuse(who, adam ? "beta1 must be in [0, 1)" : "alpha must be in [0, 1)");
+    if (adam && !(beta2 >= 0.0 && beta2 < 1.0)) return refuse(who, "beta2 must be in [0, 1)");
+    A2cLaunch L = {};
+    // RMSprop has no first moment: the list's exp_avg slots are bound to square_avg and never read
+    if (!bind_policy(L.ps, L.pg, &L.a, sh, params, grads, adam ? exp_avg : square_avg, square_avg, step))
+        return refuse(who, "null parameter, gradient or optimizer-state tensor");
+    if (!adam)
+        for (int k = 0; k < sh.n; ++k) L.a.exp_avg[k] = nullptr;
+    L.obs_dim = sh.obs_dim;
+    L.nwg = (int)ppo_nwg(batch);
+    L.adv_part = (double*)workspace;
+    L.pack = (float*)((char*)workspace + 2 * ppo::kAdvPart * sizeof(double));
+    L.part = L.pack + 2 * sh.pack;
+    L.normw = (float*)((char*)workspace + (ppo_bytes(sh, batch) + 15) / 16 * 16);
+    L.nbp = (int)((L.a.wstart[sh.n] + kAdamThreads - 1) / kAdamThreads);
+    L.obs = obs;
+    L.actions = actions;
+    L.advantages = advantages;
+    L.returns = returns;
+    L.idx = idx;
+    L.batch = batch;
+    L.normalize = normalize_advantage != 0;
+    L.ent = ent_coef;
+    L.vf = vf_coef;
+    L.max_norm = max_grad_norm;
+    L.optimizer = optimizer;
+    L.lr = lr;
+    L.eps = eps;
+    if (adam) {
+        set_adam(L, lr, alpha_or_beta1, beta2, eps);
+    } else {
+        L.alpha = (float)alpha_or_beta1;
+        L.w1 = (float)(1.0 - alpha_or_beta1);
+    }
+    L.stats = stats;
+    const hipError_t err = (hipError_t)rrc_launch_a2c(&L, stream);
+    return err == hipSuccess ? RR_OK : hip_fail(err, "rr_a2c_update: launch");
 }
 
 // ---- the Categorical policy (discrete/rocket_discrete.hip): obs_dim 7, 2 .. 4 choices on <7, 4> images ----

@@ -47,7 +47,9 @@
 // includes the same two bodies; discrete/rocket_discrete.hip (rr_ppo_update_discrete, the Categorical
 // policy) the pi tower with LOSS 2 over <7, 4> and the same two bodies; bc_discrete/rocket_bc_discrete.hip
 // (rr_bc_update_discrete, behaviour cloning of the Categorical policy) the pi tower with LOSS 3 over
-// <7, 4>, LOSS 2's head with LOSS 1's derivative, and the same two bodies.
+// <7, 4>, LOSS 2's head with LOSS 1's derivative, and the same two bodies; a2c/rocket_a2c.hip (rr_a2c_update,
+// SB3's A2C) the pi tower with LOSS 4, LOSS 0's Gaussian head with d loss / d log_prob = -A / B, beside the
+// unclipped vf tower, the finish body and an optimizer body of its own (RMSprop) or the Adam one.
 #pragma once
 
 #include <type_traits>
@@ -102,7 +104,7 @@ struct Part {
     static constexpr int HW = B2 + 64;          // [ACT][64 unit] (vf: row 0)
     static constexpr int HB = HW + 64 * ACT;    // [4]
     static constexpr int LS = HB + 4;           // [4] (pi)
-    static constexpr int ST = LS + 4;           // pi: pg sum, clip count, approx-kl sum (LOSS 2: + entropy sum; LOSS 3: -logp, exp(logp), spare, entropy); vf: squared-error sum
+    static constexpr int ST = LS + 4;           // pi: pg sum, clip count, approx-kl sum (LOSS 2: + entropy sum; LOSS 3: -logp, exp(logp), spare, entropy; LOSS 4: -A logp, logp); vf: squared-error sum
     static constexpr int SIZE = ST + 4;
     static_assert(SIZE % 4 == 0, "16-B rows");
 };
@@ -304,6 +306,10 @@ __global__ __launch_bounds__(256) void ppo_prep_kernel(const float* __restrict__
 // cloning loss's ent_weight:
 //   dz_k = -(1 / B) ((k == a) - p_k) + ent_weight / B p_k (log p_k + H),   0 for k >= n_choices;
 // no ratio, no clip; old_lp / adv are not read. The four sums are -log_prob, exp(log_prob), a spare and H.
+// LOSS 4 (A2C, a2c/rocket_a2c.hip; pi tower): LOSS 0's Gaussian head under SB3 A2C.train's policy loss
+// -mean(A log_prob), so d loss / d log_prob = -A / B with A the normalised advantage (NORM: LOSS 0's
+// statistics and float-pair mean) or adv[idx] as it is. No ratio, no clip: adv is gathered, old_lp is not
+// read (null is legal). The sums are -A log_prob (the policy loss times B), log_prob and a spare.
 template <int OBS, int ACT, int TW, bool VCLIP = false, bool NORM = true, int LOSS = 0>
 __device__ __forceinline__ void ppo_grad_tower(
     float* __restrict__ lds, const float* __restrict__ obs, const float* __restrict__ act,
@@ -321,6 +327,7 @@ __device__ __forceinline__ void ppo_grad_tower(
     constexpr int tw = TW;
     constexpr bool CAT = LOSS == 2 || LOSS == 3;    // the softmax head
     constexpr bool CLONE = LOSS == 1 || LOSS == 3;  // d loss / d log_prob = -1 / B: no ratio
+    constexpr bool A2C = LOSS == 4;                 // d loss / d log_prob = -A / B: no ratio
     const int lane = threadIdx.x & (kWave - 1), half = lane >> 5, j = lane & 31;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     float* sp = lds;
@@ -356,7 +363,9 @@ __device__ __forceinline__ void ppo_grad_tower(
 #pragma unroll
                 for (int a = 0; a < ACT; ++a) in.a[a] = act[r * ACT + a];
             }
-            if constexpr (!CLONE) {
+            if constexpr (A2C) {
+                in.av = adv[r];
+            } else if constexpr (!CLONE) {
                 in.olp = old_lp[r];
                 in.av = adv[r];
             }
@@ -502,6 +511,8 @@ __device__ __forceinline__ void ppo_grad_tower(
             float dlp, lr, r, u, c;
             if constexpr (CLONE) {
                 dlp = valid ? -inv_b : 0.0f;
+            } else if constexpr (A2C) {
+                dlp = valid ? -inv_b * A : 0.0f;
             } else {
                 lr = lp - in.olp;
                 r = expf(lr);
@@ -537,6 +548,9 @@ __device__ __forceinline__ void ppo_grad_tower(
                     st0 -= lp;
                     st1 += expf(lp);
                     if constexpr (LOSS == 3) st3 += H;
+                } else if constexpr (A2C) {
+                    st0 -= A * lp;
+                    st1 += lp;
                 } else {
                     st0 -= fminf(u, c);
                     st1 += fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
@@ -902,6 +916,25 @@ struct BcLaunch {
     float* sink;
 };
 static_assert(std::is_trivially_copyable_v<BcLaunch>, "BcLaunch crosses TUs by memcpy");
+
+// rr_a2c_update's launches (a2c/rocket_a2c.hip, rrc_launch_a2c): the advantage sums and the packing, the
+// gradient of both towers on nwg workgroups each, the finish, the optimizer. a.exp_avg_sq holds the
+// optimizer's second-moment tensors (RMSprop's square_avg, Adam's exp_avg_sq); a.exp_avg is Adam's only.
+struct A2cLaunch {
+    PolSrc ps;
+    PolGrad pg;
+    AdamList a;
+    const float *obs, *actions, *advantages, *returns, *lr;
+    const int64_t* idx;
+    int64_t batch;
+    float ent, vf, max_norm, alpha, beta1, beta2, w1, w2, eps;
+    float* stats;  // 8 floats or null
+    double* adv_part;
+    float *part, *pack, *normw;
+    int obs_dim, nwg, nbp, normalize;
+    int optimizer;  // RR_A2C_RMSPROP / RR_A2C_RMSPROP_TF / RR_A2C_ADAM
+};
+static_assert(std::is_trivially_copyable_v<A2cLaunch>, "A2cLaunch crosses TUs by memcpy");
 
 // What the main TU hands to discrete/rocket_discrete.hip (rrc_launch_discrete), by `op`:
 //   kDiscAct        rr_policy_act_discrete: one discrete_act_kernel launch

@@ -1,7 +1,8 @@
 // rocket_ppo_adam_body.inc — the body of rr_ppo_update's optimizer kernel, included as text inside
 // the kernels that share it: adam_chain_kernel (rocket_ppo.inc) and ppo_opts_adam_kernel
 // (ppo_opts/rocket_ppo_opts.hip, which obeys the control block before it and counts the step after
-// it); bc_adam_kernel (bc/rocket_bc.hip) sets max_norm 0 and an empty nx. Text and not a function
+// it); bc_adam_kernel (bc/rocket_bc.hip) sets max_norm 0 and an empty nx; a2c_adam_kernel (a2c/rocket_a2c.hip,
+// SB3's use_rms_prop=False) an empty nx. Text and not a function
 // for rocket_ppo_finish_body.inc's reason. In scope where it is included: OBS, ACT and the kernel's
 // arguments (A, normw, n_norm, max_norm, lr_p, beta1, beta2, w1, w2, eps, pack, nx, nbp). A block past
 // nbp returns from inside it.

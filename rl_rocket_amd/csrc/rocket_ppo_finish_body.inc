@@ -1,7 +1,8 @@
 // rocket_ppo_finish_body.inc — the body of the learner's finish kernel, included as text inside the
 // kernels that share it: ppo_finish_kernel (rocket_ppo.inc; CTL false) and ppo_opts_finish_kernel
 // (ppo_opts/rocket_ppo_opts.hip; CTL true, `ca` its ppo::CtlArgs); bc_finish_kernel (bc/rocket_bc.hip;
-// CTL false, stats null, nwg 0 for the value half) adds its own lines after it. Text and not a function: taken
+// CTL false, stats null, nwg 0 for the value half) adds its own lines after it; a2c_finish_kernel
+// (a2c/rocket_a2c.hip; CTL false, stats null) its statistics in a block row of its own. Text and not a function: taken
 // through a call, even an inlined one, ppo_finish_kernel's machine code changed. In scope where it
 // is included: OBS, ACT, CTL, ca and the kernel's arguments (part, nwg, bs, ent_coef, src, dst,
 // stats, normw, step0).
