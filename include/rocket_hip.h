@@ -896,6 +896,39 @@ int rr_bc_update_discrete(int obs_dim, int n_choices, float* const* params, floa
                           const float* lr, double beta1, double beta2, float eps, float* stats, uint32_t flags,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* One A2C update of this policy (a pure addition to ABI 14), rr_a2c_update for the Categorical policy: rows
+ * idx[0 .. batch) of a device rollout whose actions are [M], the chosen index as a float (what
+ * rr_policy_act_discrete and the one-launch collect write); stable_baselines3 A2C.train() behind a
+ * CategoricalDistribution, loss.backward(), clip_grad_norm_ and the optimizer's step:
+ *   A    = advantages[idx], or with normalize_advantage != 0 (A - mean(A)) / (std(A) + 1e-8)
+ *   lp_i = z_{i, a_i} - logsumexp_k z_ik          over the first n_choices logits
+ *   H_i  = -sum_k p_ik log p_ik                   (0 for a term whose p_ik is 0)
+ *   policy_loss = -mean(A lp),   value_loss = mean((returns - V)^2),   entropy = mean(H)
+ *   loss        = policy_loss - ent_coef entropy + vf_coef value_loss
+ *   d loss / d z_ik = -(A_i / B) ((k == a_i) - p_ik) + ent_coef / B p_ik (log p_ik + H_i),  0 for k >= n_choices
+ * There is no probability ratio: the rollout's stored log-probs are not an argument. The five tensor lists
+ * have 12 entries, in rr_ppo_update_discrete's order; `optimizer`, square_avg, exp_avg (NULL unless
+ * RR_A2C_ADAM), step, alpha_or_beta1, beta2, eps, max_grad_norm (0: no clip) and lr (a device float) are
+ * rr_a2c_update's, and all 12 step tensors count the call. stats is a device block of RR_A2C_STAT_SLOTS
+ * floats or NULL: [policy_loss, value_loss, mean H, loss, mean lp, 0, 0, 0] (the RR_A2C_STAT_* slots).
+ * One call is four launches (advantage sums and packing, gradient, finish, optimizer). Capturable in a
+ * graph; deterministic (fixed-order sums, no atomics). The workspace holds the call's intermediates and a
+ * sink of [4][64] + [4] floats for the heads >= n_choices; no state is read from it: its contents before
+ * the call do not matter.
+ * actions MUST hold integers in [0, n_choices): the call cannot check device data. It guarantees only
+ * that no address depends on them (an index is compared against k, never used as an offset).
+ * RR_EINVAL before any launch for obs_dim != 7, n_choices outside 2 .. 4, batch < 2, a null argument or
+ * tensor, an unknown optimizer, NaN, infinite or negative ent_coef / vf_coef / max_grad_norm / eps,
+ * alpha_or_beta1 or beta2 outside [0, 1), a workspace too small or not 16-B aligned. workspace:
+ * rr_a2c_update_discrete_workspace_size bytes. */
+int rr_a2c_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes);
+int rr_a2c_update_discrete(int obs_dim, int n_choices, float* const* params, float* const* grads,
+                           float* const* square_avg, float* const* exp_avg, float* const* step, const float* obs,
+                           const float* actions, const float* advantages, const float* returns, const int64_t* idx,
+                           int64_t batch, int normalize_advantage, float ent_coef, float vf_coef, float max_grad_norm,
+                           int optimizer, const float* lr, double alpha_or_beta1, double beta2, float eps,
+                           float* stats, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The one-launch collect, its per-step form and the one-launch evaluation for this policy (pure
  * additions to ABI 14: a caller that needs them looks the symbols up). The handle is a 3DOF one with
  * an RK4 or Euler integrator, params an image of rr_policy_pack_discrete (16-B aligned), precision

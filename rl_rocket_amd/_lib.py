@@ -233,6 +233,11 @@ SIGNATURES = {
     "rr_a2c_update": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 10 +
                       [ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, _P,
                        ctypes.c_double, ctypes.c_double, ctypes.c_float, _P, _P, ctypes.c_int64, _P]),
+    "rr_a2c_update_discrete_workspace_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, _P]),
+    "rr_a2c_update_discrete": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [_P] * 10 +
+                               [ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                ctypes.c_int, _P, ctypes.c_double, ctypes.c_double, ctypes.c_float, _P, _P,
+                                ctypes.c_int64, _P]),
     "rr_policy_layout_discrete": (ctypes.c_int, [ctypes.c_int, _P]),
     "rr_policy_pack_discrete": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, _P, _P]),
     "rr_policy_act_discrete": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, ctypes.c_int64,

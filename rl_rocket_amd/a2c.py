@@ -19,6 +19,10 @@ The loss is SB3 1.6 ``A2C.train``'s for the ``MlpPolicy`` actor-critic with a di
 then ``clip_grad_norm_(max_grad_norm)`` and ``optimizer.step()``. There is no probability ratio, so the
 rollout's stored log-probs are never read: a rollout of any ``policy_dtype`` goes through the same call
 (the learner is fp32).
+
+A ``MlpCategoricalActorCritic`` is refused by the three classes here: its fused call has names of its own,
+``a2c_discrete.A2CUpdateDiscrete``, ``a2c_update_discrete`` and ``GraphedA2CDiscrete``
+(``rr_a2c_update_discrete``), which share this module's optimizer checks, state binding and graph capture.
 """
 import ctypes
 
@@ -120,7 +124,8 @@ def _fused_reason(policy, optimizer, ro):
     """Why ``rr_a2c_update`` does not take this policy, optimizer and rollout; None if it does."""
     if isinstance(policy, MlpCategoricalActorCritic):
         return ("the fused A2C call takes the Gaussian MlpActorCritic; the Categorical A2C call is a follow-up "
-                "(a2c_update(fused=False) runs its loss through autograd)")
+                "(a2c_update(fused=False) runs its loss through autograd); it now exists under names of its own: "
+                "a2c_discrete.A2CUpdateDiscrete, a2c_update_discrete and GraphedA2CDiscrete")
     if not fused_grad_supported(policy, ro.env.state_dim, ro.env.action_dim):
         return "the fused A2C call needs an MlpActorCritic with 64x64 towers and (obs, act) in ((14, 3), (7, 2))"
     reason = _optimizer_kind(optimizer, list(policy.parameters()))[1]
@@ -152,31 +157,40 @@ class A2CUpdate:
     It writes ``p.grad`` (after the clip), steps the 13 parameters and returns ``stats`` (device, 8 floats:
     ``STAT_NAMES``). Stream-ordered and graph-capturable. ``lr`` is read from a device scalar that eager
     calls refresh from ``param_groups[0]["lr"]``; ``sync_lr()`` before replays of a captured graph.
-    Reads ``ro.advantages`` and ``ro.returns`` and never ``ro.log_probs``."""
+    Reads ``ro.advantages`` and ``ro.returns`` and never ``ro.log_probs``. A Categorical policy is refused:
+    ``a2c_discrete.A2CUpdateDiscrete`` is this class for it."""
+
+    _call = "rr_a2c_update"  # A2CUpdateDiscrete: rr_a2c_update_discrete
 
     def __init__(self, policy, optimizer, ro, normalize_advantage=False, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5):
         self.ent_coef, self.vf_coef, self.max_norm = _coefficients(ent_coef, vf_coef, max_grad_norm)
         reason = _fused_reason(policy, optimizer, ro)
         if reason is not None:
             raise ValueError("A2CUpdate: " + reason)
+        self._bind(policy, optimizer, ro, normalize_advantage, ro.env.action_dim, ro.env.action_dim)
+
+    def _bind(self, policy, optimizer, ro, normalize_advantage, na, act_cols):
+        """What the constructor does once the policy, optimizer and rollout have passed: the call's shape is
+        ``(state_dim, na)`` and a row of ``ro.actions`` has ``act_cols`` floats."""
         self.normalize = bool(normalize_advantage)
         self.policy, self.opt = policy, optimizer
         self.kind = _optimizer_kind(optimizer, list(policy.parameters()))[0]
-        ns, na = ro.env.state_dim, ro.env.action_dim
+        ns = ro.env.state_dim
         n = ro.n_steps * ro.env.num_envs
         if n < 2:
-            raise ValueError("A2CUpdate needs a rollout of at least 2 rows")
+            raise ValueError("%s needs a rollout of at least 2 rows" % type(self).__name__)
         self._lib = _lib.load()
         self.ns, self.na, self.n = ns, na, n
         dev = ro.obs.device
-        self.data = [ro.obs.reshape(n, ns), ro.actions.reshape(n, na), ro.advantages.reshape(n), ro.returns.reshape(n)]
+        self.data = [ro.obs.reshape(n, ns), ro.actions.reshape(n, act_cols), ro.advantages.reshape(n),
+                     ro.returns.reshape(n)]
         for t in self.data:
             if not t.is_contiguous() or t.dtype != torch.float32:
                 raise ValueError("rollout tensors must be contiguous fp32")
         self.params = _policy_tensors(policy)
-        _check_params("rr_a2c_update", self.params, dev, "rollout")
+        _check_params(self._call, self.params, dev, "rollout")
         self._bind_state()
-        self.ws, self._nbytes = _workspace(self._lib, "rr_a2c_update_workspace_size", dev, ns, na, n)
+        self.ws, self._nbytes = _workspace(self._lib, self._call + "_workspace_size", dev, ns, na, n)
         self.stats = torch.zeros(_lib.RR_A2C_STAT_SLOTS, dtype=torch.float32, device=dev)
         self.lr = torch.zeros(1, dtype=torch.float32, device=dev)
         self.sync_lr()
@@ -199,7 +213,7 @@ class A2CUpdate:
                         st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st[second] = torch.zeros_like(p, memory_format=torch.preserve_format)
             if not torch.is_tensor(st["step"]) or not st["step"].is_cuda or st["step"].dtype != torch.float32:
-                raise ValueError("A2CUpdate needs the optimizer's device float32 step tensors")
+                raise ValueError("%s needs the optimizer's device float32 step tensors" % type(self).__name__)
         self._tensors = [(p, p.grad, opt.state[p][second], opt.state[p]["exp_avg"] if adam else None,
                           opt.state[p]["step"]) for p in self.params]
         P = ctypes.c_void_p * len(self.params)
@@ -217,7 +231,8 @@ class A2CUpdate:
         for p, g, sq, m, s in self._tensors:
             st = self.opt.state[p]
             if p.grad is not g or st[second] is not sq or st["step"] is not s or (adam and st["exp_avg"] is not m):
-                raise RuntimeError("a gradient or optimizer state tensor was replaced; A2CUpdate holds their addresses")
+                raise RuntimeError("a gradient or optimizer state tensor was replaced; %s holds their addresses"
+                                   % type(self).__name__)
         if not torch.cuda.is_current_stream_capturing():
             self.sync_lr()
         grp = self.opt.param_groups[0]
@@ -230,10 +245,11 @@ class A2CUpdate:
         else:
             _check_rows(idx, self.n, self.ws.device)
         kind, lr, a, b2, eps = self._opt_args()
-        _lib.check(self._lib.rr_a2c_update(self.ns, self.na, *self._ptrs, *[t.data_ptr() for t in self.data],
-                                           idx.data_ptr(), idx.numel(), int(self.normalize), self.ent_coef, self.vf_coef,
-                                           self.max_norm, kind, lr, a, b2, eps, self.stats.data_ptr(), self.ws.data_ptr(),
-                                           self._nbytes, _stream(self.ws.device)), "rr_a2c_update")
+        _lib.check(getattr(self._lib, self._call)(self.ns, self.na, *self._ptrs, *[t.data_ptr() for t in self.data],
+                                                  idx.data_ptr(), idx.numel(), int(self.normalize), self.ent_coef,
+                                                  self.vf_coef, self.max_norm, kind, lr, a, b2, eps,
+                                                  self.stats.data_ptr(), self.ws.data_ptr(), self._nbytes,
+                                                  _stream(self.ws.device)), self._call)
         self.n_updates += 1
         return self.stats
 
@@ -310,7 +326,8 @@ class GraphedA2C:
     stream on the real env, rollout, parameters and optimizer state, and is undone in place (the env through
     its ``checkpoint()`` / ``restore()`` and its output buffers), so the first ``step()`` starts where an
     eager ``ro.collect(); update()`` would and computes the same bits. ``update`` is the ``A2CUpdate``;
-    ``train_stats()`` is its."""
+    ``train_stats()`` is its. A Categorical policy is refused: ``a2c_discrete.GraphedA2CDiscrete`` is this
+    class for it."""
 
     def __init__(self, policy, optimizer, ro, normalize_advantage=False, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5):
         _coefficients(ent_coef, vf_coef, max_grad_norm)
@@ -319,8 +336,13 @@ class GraphedA2C:
             raise ValueError("GraphedA2C: " + reason)
         if not (getattr(ro, "fused", False) and getattr(ro, "one_launch", False)) or getattr(ro, "per_step", True):
             raise ValueError("GraphedA2C needs the one-launch collect (fused policy, RK4 / Euler env, not per_step)")
+        self._capture(ro, A2CUpdate(policy, optimizer, ro, normalize_advantage, ent_coef, vf_coef, max_grad_norm))
+
+    def _capture(self, ro, update):
+        """The warm-up iteration, the put-back and the capture of ``ro.collect(); update()``."""
+        optimizer = update.opt
         self.ro = ro
-        self.update = A2CUpdate(policy, optimizer, ro, normalize_advantage, ent_coef, vf_coef, max_grad_norm)
+        self.update = update
         env, dev = ro.env, ro.obs.device
         # what one iteration writes and the next one reads, to put back after the warm-up
         torch.cuda.synchronize(dev)

@@ -85,6 +85,10 @@ SRC_EVAL_SAMPLED_DISCRETE = os.path.join(HERE, "csrc", "eval_sampled_discrete", 
 # same reason, with the learner's settings
 SRC_A2C = os.path.join(HERE, "csrc", "a2c", "rocket_a2c.hip")
 INC_A2C_RMSPROP = os.path.join(HERE, "csrc", "a2c", "rocket_rmsprop_body.inc")
+# A2C for the Categorical policy (rr_a2c_update_discrete): the A2C unit's pipeline over the discrete unit's
+# images (the pi tower's softmax head with the A2C derivative, the sink for heads past K), in a module of its
+# own for the same reason, with the learner's settings; its RMSprop body is the A2C unit's .inc
+SRC_A2C_DISCRETE = os.path.join(HERE, "csrc", "a2c_discrete", "rocket_a2c_discrete.hip")
 HEADER = os.path.join(ROOT, "include", "rocket_hip.h")
 OUT = os.path.join(HERE, "librocket_hip.so")
 # benchmark-only helper (not part of the product ABI): bench.py's event-timed direct-launch region
@@ -120,12 +124,12 @@ def command(resource_usage=False, out=OUT, defines=(), extra=(), src=SRC, compil
 
 
 def sources():
-    """Every file the nineteen translation units are compiled from: all of csrc/ (three units and the
+    """Every file the twenty translation units are compiled from: all of csrc/ (three units and the
     text the others include, the behaviour-cloning kernels' rocket_bc.inc among it), the recording and
     the exact-mode evaluation's units, the statistics collect's unit with the .inc beside it, the
     learner-options, behaviour-cloning, discrete-action, discrete behaviour-cloning, discrete-rollout,
     discrete learner-options, discrete statistics-collect, discrete recording-evaluation, recording
-    exact-evaluation, discrete exact-evaluation, the two sampled-evaluation and the A2C units (the latter with the .inc beside it)
+    exact-evaluation, discrete exact-evaluation, the two sampled-evaluation, the A2C (with the .inc beside it) and the discrete A2C units
     and the C-ABI header, sorted (tests/test_build_sources.py checks that the
     #include graph stays inside this list)."""
     csrc = os.path.join(HERE, "csrc")
@@ -133,7 +137,7 @@ def sources():
                   + [SRC_EVAL_TRACE, SRC_EVAL_EXACT, SRC_COLLECT_STATS, INC_COLLECT_STATS, SRC_PPO_OPTS, SRC_BC, SRC_DISCRETE,
                      SRC_BC_DISCRETE, SRC_ROLLOUT_DISCRETE, SRC_DISCRETE_OPTS, SRC_COLLECT_STATS_DISCRETE,
                      SRC_EVAL_TRACE_DISCRETE, SRC_EVAL_EXACT_TRACE, SRC_EVAL_EXACT_DISCRETE, SRC_EVAL_SAMPLED,
-                     SRC_EVAL_SAMPLED_DISCRETE, SRC_A2C, INC_A2C_RMSPROP, HEADER])
+                     SRC_EVAL_SAMPLED_DISCRETE, SRC_A2C, INC_A2C_RMSPROP, SRC_A2C_DISCRETE, HEADER])
 
 
 def source_hash():
@@ -152,12 +156,12 @@ def source_hash():
 
 
 def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
-    """The six hipcc calls that build the library's nineteen translation units: the main, exact-mode,
+    """The six hipcc calls that build the library's twenty translation units: the main, exact-mode,
     collect, recording-evaluation and exact-evaluation units compiled to objects (the latter four with EXACT_FLAGS /
     COLLECT_FLAGS / COLLECT_FLAGS / EVAL_EXACT_FLAGS); the last step compiles the learner-options, the
     behaviour-cloning, the discrete-action, the discrete behaviour-cloning, the discrete-rollout, the discrete
     learner-options, the discrete statistics-collect, the discrete recording-evaluation, the recording exact-evaluation, the
-    discrete exact-evaluation, the two sampled-evaluation, the A2C and the statistics collect's units
+    discrete exact-evaluation, the two sampled-evaluation, the A2C, the discrete A2C and the statistics collect's units
     (all COLLECT_FLAGS, each a module of its own) and links them with
     those objects into `out` in one hipcc call. The flags of that call reach only the sources it
     compiles: the objects already hold their code objects."""
@@ -181,14 +185,15 @@ def commands(resource_usage=False, out=OUT, defines=(), extra=(), preload=4):
                                                                             SRC_EVAL_EXACT_DISCRETE,
                                                                             SRC_EVAL_SAMPLED,
                                                                             SRC_EVAL_SAMPLED_DISCRETE,
-                                                                            SRC_A2C],
+                                                                            SRC_A2C,
+                                                                            SRC_A2C_DISCRETE],
                  SRC_COLLECT_STATS,
                  preload=preload)
     return [c1, c2, c3, c4, c5, c6]
 
 
 def build_lib(out=OUT, defines=(), extra=(), resource_usage=False, verbose=True, preload=4):
-    """Compile five translation units to objects (in parallel), then the other fourteen in the call that
+    """Compile five translation units to objects (in parallel), then the other fifteen in the call that
     links `out`."""
     cmds = commands(resource_usage, out, defines, extra, preload=preload)
     if verbose:

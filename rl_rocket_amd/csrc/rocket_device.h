@@ -1245,6 +1245,9 @@ __attribute__((visibility("hidden"))) int rrc_launch_discrete(const void* launch
 __attribute__((visibility("hidden"))) int rrc_launch_bc_discrete(const void* launch, void* stream);
 // a2c/rocket_a2c.hip: rr_a2c_update's launches, an A2cLaunch
 __attribute__((visibility("hidden"))) int rrc_launch_a2c(const void* launch, void* stream);
+// a2c_discrete/rocket_a2c_discrete.hip: rr_a2c_update_discrete's launches, an A2cDiscreteLaunch (rocket_ppo.inc,
+// beside the A2cLaunch it extends)
+__attribute__((visibility("hidden"))) int rrc_launch_a2c_discrete(const void* launch, void* stream);
 // rollout_discrete/rocket_rollout_discrete.hip: the Categorical policy's one-launch collect (multi != 0),
 // its per-step launch and its one-launch evaluation; head points to the caller's DiscHead
 __attribute__((visibility("hidden"))) int rrc_launch_rollout_discrete(const void* launch, const void* io, const void* head,

@@ -385,6 +385,7 @@ __attribute__((weak)) int rrc_launch_bc(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_discrete(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_bc_discrete(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_a2c(const void*, void*) { return kNoUnit; }
+__attribute__((weak)) int rrc_launch_a2c_discrete(const void*, void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_rollout_discrete(const void*, const void*, const void*, int) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_eval_discrete(const void*, const void*, const void*) { return kNoUnit; }
 __attribute__((weak)) int rrc_launch_discrete_opts(const void*, void*) { return kNoUnit; }
@@ -2143,24 +2144,24 @@ int rr_a2c_update_workspace_size(int obs_dim, int act_dim, int64_t batch, int64_
     return rc;
 }
 
-int rr_a2c_update(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* square_avg,
-                  float* const* exp_avg, float* const* step, const float* obs, const float* actions,
-                  const float* advantages, const float* returns, const int64_t* idx, int64_t batch,
-                  int normalize_advantage, float ent_coef, float vf_coef, float max_grad_norm, int optimizer,
-                  const float* lr, double alpha_or_beta1, double beta2, float eps, float* stats,
-                  void* workspace, int64_t workspace_bytes, void* stream)
+namespace {
+// rr_a2c_update's and rr_a2c_update_discrete's checks after the shape's (nothing is launched before they
+// pass) and the launch record over the shape's tensors; ws_need is the call's *_workspace_size, whose first
+// ppo_update_bytes are carved here (the Categorical call's sink follows them).
+int a2c_update_record(const char* who, A2cLaunch& L, const LearnerShape& sh, float* const* params, float* const* grads,
+                      float* const* square_avg, float* const* exp_avg, float* const* step, const float* obs,
+                      const float* actions, const float* advantages, const float* returns, const int64_t* idx,
+                      int64_t batch, int normalize_advantage, float ent_coef, float vf_coef, float max_grad_norm,
+                      int optimizer, const float* lr, double alpha_or_beta1, double beta2, float eps, float* stats,
+                      void* workspace, int64_t workspace_bytes, int64_t ws_need)
 {
-    const char* who = "rr_a2c_update";
-    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
-    if (const int rc = learner_shape_ok(who, sh, batch, nullptr, false); rc != RR_OK) return rc;
     if (optimizer != RR_A2C_RMSPROP && optimizer != RR_A2C_RMSPROP_TF && optimizer != RR_A2C_ADAM)
         return refuse(who, "optimizer must be RR_A2C_RMSPROP, RR_A2C_RMSPROP_TF or RR_A2C_ADAM");
     const bool adam = optimizer == RR_A2C_ADAM;
     if (!params || !grads || !square_avg || (adam && !exp_avg) || !step || !obs || !actions || !advantages || !returns ||
         !idx || !lr)
         return refuse(who, "null argument");
-    if (const int rc = learner_ws_ok(who, workspace, workspace_bytes, ppo_update_bytes(sh, batch), 0, 0); rc != RR_OK)
-        return rc;
+    if (const int rc = learner_ws_ok(who, workspace, workspace_bytes, ws_need, 0, 0); rc != RR_OK) return rc;
     // NaN fails every comparison: !(x >= 0 && x < inf) is true for NaN, negatives and infinities
     if (!(ent_coef >= 0.0f && ent_coef < HUGE_VALF)) return refuse(who, "ent_coef must be finite and >= 0");
     if (!(vf_coef >= 0.0f && vf_coef < HUGE_VALF)) return refuse(who, "vf_coef must be finite and >= 0");
@@ -2170,7 +2171,7 @@ int rr_a2c_update(int obs_dim, int act_dim, float* const* params, float* const* 
     if (!(alpha_or_beta1 >= 0.0 && alpha_or_beta1 < 1.0))
         return refuse(who, adam ? "beta1 must be in [0, 1)" : "alpha must be in [0, 1)");
     if (adam && !(beta2 >= 0.0 && beta2 < 1.0)) return refuse(who, "beta2 must be in [0, 1)");
-    A2cLaunch L = {};
+    L = {};
     // RMSprop has no first moment: the list's exp_avg slots are bound to square_avg and never read
     if (!bind_policy(L.ps, L.pg, &L.a, sh, params, grads, adam ? exp_avg : square_avg, square_avg, step))
         return refuse(who, "null parameter, gradient or optimizer-state tensor");
@@ -2203,6 +2204,26 @@ int rr_a2c_update(int obs_dim, int act_dim, float* const* params, float* const* 
         L.w1 = (float)(1.0 - alpha_or_beta1);
     }
     L.stats = stats;
+    return RR_OK;
+}
+}  // namespace
+
+int rr_a2c_update(int obs_dim, int act_dim, float* const* params, float* const* grads, float* const* square_avg,
+                  float* const* exp_avg, float* const* step, const float* obs, const float* actions,
+                  const float* advantages, const float* returns, const int64_t* idx, int64_t batch,
+                  int normalize_advantage, float ent_coef, float vf_coef, float max_grad_norm, int optimizer,
+                  const float* lr, double alpha_or_beta1, double beta2, float eps, float* stats,
+                  void* workspace, int64_t workspace_bytes, void* stream)
+{
+    const char* who = "rr_a2c_update";
+    const LearnerShape sh = gauss_shape(obs_dim, act_dim);
+    if (const int rc = learner_shape_ok(who, sh, batch, nullptr, false); rc != RR_OK) return rc;
+    A2cLaunch L;
+    const int rc = a2c_update_record(who, L, sh, params, grads, square_avg, exp_avg, step, obs, actions, advantages,
+                                     returns, idx, batch, normalize_advantage, ent_coef, vf_coef, max_grad_norm, optimizer,
+                                     lr, alpha_or_beta1, beta2, eps, stats, workspace, workspace_bytes,
+                                     ppo_update_bytes(sh, batch));
+    if (rc != RR_OK) return rc;
     const hipError_t err = (hipError_t)rrc_launch_a2c(&L, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_a2c_update: launch");
 }
@@ -2585,6 +2606,39 @@ int rr_bc_update_discrete(int obs_dim, int n_choices, float* const* params, floa
     L.pg.p[12] = L.sink + 64 * 4 + 4;  // log_std's slot of the finish body
     const hipError_t err = (hipError_t)rrc_launch_bc_discrete(&L, stream);
     return err == hipSuccess ? RR_OK : hip_fail(err, "rr_bc_update_discrete: launch");
+}
+
+// ---- A2C for the Categorical policy (a2c_discrete/rocket_a2c_discrete.hip): rr_a2c_update's record over the
+// 12 tensors, rr_ppo_update_discrete's workspace (rr_ppo_update's sections, then the sink) ----
+int rr_a2c_update_discrete_workspace_size(int obs_dim, int n_choices, int64_t batch, int64_t* bytes)
+{
+    const int rc = disc_learner_ok("rr_a2c_update_discrete_workspace_size", obs_dim, n_choices, batch, bytes);
+    if (rc == RR_OK) *bytes = ppo_update_bytes(disc_shape(n_choices), batch) + kDiscSink * (int64_t)sizeof(float);
+    return rc;
+}
+
+int rr_a2c_update_discrete(int obs_dim, int n_choices, float* const* params, float* const* grads,
+                           float* const* square_avg, float* const* exp_avg, float* const* step, const float* obs,
+                           const float* actions, const float* advantages, const float* returns, const int64_t* idx,
+                           int64_t batch, int normalize_advantage, float ent_coef, float vf_coef, float max_grad_norm,
+                           int optimizer, const float* lr, double alpha_or_beta1, double beta2, float eps, float* stats,
+                           void* workspace, int64_t workspace_bytes, void* stream)
+{
+    const char* who = "rr_a2c_update_discrete";
+    if (const int rc = disc_learner_ok(who, obs_dim, n_choices, batch, nullptr, false); rc != RR_OK) return rc;
+    const LearnerShape sh = disc_shape(n_choices);
+    const int64_t sink_at = ppo_update_bytes(sh, batch);
+    A2cDiscreteLaunch D = {};
+    const int rc = a2c_update_record(who, D.base, sh, params, grads, square_avg, exp_avg, step, obs, actions, advantages,
+                                     returns, idx, batch, normalize_advantage, ent_coef, vf_coef, max_grad_norm, optimizer,
+                                     lr, alpha_or_beta1, beta2, eps, stats, workspace, workspace_bytes,
+                                     sink_at + kDiscSink * (int64_t)sizeof(float));
+    if (rc != RR_OK) return rc;
+    D.n_choices = n_choices;
+    D.sink = (float*)((char*)workspace + sink_at);
+    D.base.pg.p[12] = D.sink + 64 * 4 + 4;  // log_std's slot of the finish body
+    const hipError_t err = (hipError_t)rrc_launch_a2c_discrete(&D, stream);
+    return err == hipSuccess ? RR_OK : hip_fail(err, "rr_a2c_update_discrete: launch");
 }
 
 }  // extern "C"

@@ -49,7 +49,9 @@
 // (rr_bc_update_discrete, behaviour cloning of the Categorical policy) the pi tower with LOSS 3 over
 // <7, 4>, LOSS 2's head with LOSS 1's derivative, and the same two bodies; a2c/rocket_a2c.hip (rr_a2c_update,
 // SB3's A2C) the pi tower with LOSS 4, LOSS 0's Gaussian head with d loss / d log_prob = -A / B, beside the
-// unclipped vf tower, the finish body and an optimizer body of its own (RMSprop) or the Adam one.
+// unclipped vf tower, the finish body and an optimizer body of its own (RMSprop) or the Adam one;
+// a2c_discrete/rocket_a2c_discrete.hip (rr_a2c_update_discrete, A2C for the Categorical policy) the pi tower
+// with LOSS 5 over <7, 4>, LOSS 2's head with LOSS 4's derivative, and the A2C unit's other pieces.
 #pragma once
 
 #include <type_traits>
@@ -104,7 +106,7 @@ struct Part {
     static constexpr int HW = B2 + 64;          // [ACT][64 unit] (vf: row 0)
     static constexpr int HB = HW + 64 * ACT;    // [4]
     static constexpr int LS = HB + 4;           // [4] (pi)
-    static constexpr int ST = LS + 4;           // pi: pg sum, clip count, approx-kl sum (LOSS 2: + entropy sum; LOSS 3: -logp, exp(logp), spare, entropy; LOSS 4: -A logp, logp); vf: squared-error sum
+    static constexpr int ST = LS + 4;           // pi: pg sum, clip count, approx-kl sum (LOSS 2: + entropy sum; LOSS 3: -logp, exp(logp), spare, entropy; LOSS 4: -A logp, logp; LOSS 5: -A logp, logp, spare, entropy); vf: squared-error sum
     static constexpr int SIZE = ST + 4;
     static_assert(SIZE % 4 == 0, "16-B rows");
 };
@@ -310,6 +312,12 @@ __global__ __launch_bounds__(256) void ppo_prep_kernel(const float* __restrict__
 // -mean(A log_prob), so d loss / d log_prob = -A / B with A the normalised advantage (NORM: LOSS 0's
 // statistics and float-pair mean) or adv[idx] as it is. No ratio, no clip: adv is gathered, old_lp is not
 // read (null is legal). The sums are -A log_prob (the policy loss times B), log_prob and a spare.
+// LOSS 5 (A2C for the Categorical policy, a2c_discrete/rocket_a2c_discrete.hip; pi tower over <OBS, 4>):
+// LOSS 2's softmax and entropy lines with LOSS 4's dlp = -A / B (A gathered, normalised under NORM) and
+// ent_coef an argument:
+//   dz_k = -(A / B) ((k == a) - p_k) + ent_coef / B p_k (log p_k + H),   0 for k >= n_choices;
+// no ratio, no clip; old_lp is not read (null is legal). The four sums are -A log_prob, log_prob, a spare
+// and H.
 template <int OBS, int ACT, int TW, bool VCLIP = false, bool NORM = true, int LOSS = 0>
 __device__ __forceinline__ void ppo_grad_tower(
     float* __restrict__ lds, const float* __restrict__ obs, const float* __restrict__ act,
@@ -325,9 +333,9 @@ __device__ __forceinline__ void ppo_grad_tower(
     constexpr int KP1 = L::KP1;
     constexpr int TS = ppo::kTS;
     constexpr int tw = TW;
-    constexpr bool CAT = LOSS == 2 || LOSS == 3;    // the softmax head
-    constexpr bool CLONE = LOSS == 1 || LOSS == 3;  // d loss / d log_prob = -1 / B: no ratio
-    constexpr bool A2C = LOSS == 4;                 // d loss / d log_prob = -A / B: no ratio
+    constexpr bool CAT = LOSS == 2 || LOSS == 3 || LOSS == 5;  // the softmax head
+    constexpr bool CLONE = LOSS == 1 || LOSS == 3;             // d loss / d log_prob = -1 / B: no ratio
+    constexpr bool A2C = LOSS == 4 || LOSS == 5;               // d loss / d log_prob = -A / B: no ratio
     const int lane = threadIdx.x & (kWave - 1), half = lane >> 5, j = lane & 31;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     float* sp = lds;
@@ -433,7 +441,7 @@ __device__ __forceinline__ void ppo_grad_tower(
         for (int r = 0; r < 16; ++r) accW1[b][r] = 0.0f;
     float hw_acc[ACT], hb_acc[ACT], ls_acc[ACT], b2_acc = 0.0f;
     float st0 = 0.0f, st1 = 0.0f, st2 = 0.0f;
-    [[maybe_unused]] float st3 = 0.0f;  // LOSS 2 / 3: the entropy sum
+    [[maybe_unused]] float st3 = 0.0f;  // LOSS 2 / 3 / 5: the entropy sum
 #pragma unroll
     for (int a = 0; a < ACT; ++a) hw_acc[a] = hb_acc[a] = ls_acc[a] = 0.0f;
     float ls[ACT], var[ACT];
@@ -551,6 +559,7 @@ __device__ __forceinline__ void ppo_grad_tower(
                 } else if constexpr (A2C) {
                     st0 -= A * lp;
                     st1 += lp;
+                    if constexpr (LOSS == 5) st3 += H;
                 } else {
                     st0 -= fminf(u, c);
                     st1 += fabsf(r - 1.0f) > clip ? 1.0f : 0.0f;
@@ -935,6 +944,16 @@ struct A2cLaunch {
     int optimizer;  // RR_A2C_RMSPROP / RR_A2C_RMSPROP_TF / RR_A2C_ADAM
 };
 static_assert(std::is_trivially_copyable_v<A2cLaunch>, "A2cLaunch crosses TUs by memcpy");
+
+// rr_a2c_update_discrete's launches (a2c_discrete/rocket_a2c_discrete.hip, rrc_launch_a2c_discrete): an
+// rr_a2c_update launch record over 12 tensors whose pg.p[12] is four spare floats of the workspace, the
+// number of choices, and `sink`, 260 more floats (where the finish puts the zero sums of heads >= n_choices)
+struct A2cDiscreteLaunch {
+    A2cLaunch base;
+    int n_choices;
+    float* sink;
+};
+static_assert(std::is_trivially_copyable_v<A2cDiscreteLaunch>, "A2cDiscreteLaunch crosses TUs by memcpy");
 
 // What the main TU hands to discrete/rocket_discrete.hip (rrc_launch_discrete), by `op`:
 //   kDiscAct        rr_policy_act_discrete: one discrete_act_kernel launch

@@ -12,11 +12,12 @@ reward += gamma * V(terminal_obs) where TimeLimit truncated the episode.
 
 This module holds the collector, ``DeviceRollout``, and is the import surface of what works on its
 buffers: the policy and its packer (``policy.py``), the PPO learner (``learner.py``), the evaluator
-(``evaluate.py``), behaviour cloning (``bc.py``) and A2C (``a2c.py``) are re-exported below, the same objects.
+(``evaluate.py``), behaviour cloning (``bc.py``) and A2C (``a2c.py``, ``a2c_discrete.py``) are re-exported below, the same objects.
 """
 import torch
 
 from .a2c import A2CUpdate, GraphedA2C, RMSpropTFLike, a2c_update  # noqa: F401
+from .a2c_discrete import A2CUpdateDiscrete, GraphedA2CDiscrete, a2c_update_discrete  # noqa: F401
 from .bc import BCUpdate, Demonstrations, bc_train  # noqa: F401
 from .evaluate import (EVAL_BOUNDS, EVAL_EVENT, EVAL_LANDED, EVAL_NONFINITE, EVAL_TRUNCATED,  # noqa: F401
                        EpisodeRecord, EvalResult, EvalTrace, PolicyEvaluator, evaluate_policy)
