@@ -93,14 +93,9 @@ __global__ __launch_bounds__(pol::kThreads) void discrete_act_kernel(
     key = mix32(key ^ (uint32_t)it ^ seed_hi);
     key = mix32(key ^ (uint32_t)(it >> 32) ^ (t * 0x9E3779B9u));
     const float u = (float)(mix32(key) >> 8) * 0x1p-24f;  // [0, 1)
-    // index = the number of k in 0 .. K - 2 whose running sum p_0 + .. + p_k is <= u
-    int index = 0;
-    float c = 0.0f;
-#pragma unroll
-    for (int k = 0; k < NL - 1; ++k) {
-        c += ex[k] / sum;
-        index += (k < n_choices - 1 && c <= u) ? 1 : 0;
-    }
+    // index = the number of k in 0 .. K - 2 whose running sum p_0 + .. + p_k is <= u and which have a
+    // positive weight beyond them: a choice whose weight underflowed to 0 is never drawn
+    const int index = categorical_index(ex, sum, u, n_choices);
     // the chosen logit and the table row by compares: no data-dependent address
     float za = z[0], a0 = tab.v[0][0], a1 = tab.v[0][1];
 #pragma unroll

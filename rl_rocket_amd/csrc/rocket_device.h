@@ -335,6 +335,34 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x)
     return x;
 }
 
+// The Categorical sampler's index (discrete_act_kernel, rocket_rollout_body.inc, rocket_eval_body.inc): the
+// number of q in 0 .. K - 2 whose running sum of ex / sum is <= u, where a step past choice q counts only
+// while some weight beyond q is positive. ex holds the softmax weights exp(z - max), 0 for the heads
+// >= n_choices, and sum their fp32 sum. u reaches 1 - 2^-24 and the fp32 running sum over the live choices
+// can stop one to three ulps short of 1: without the second condition the index then walked past the last
+// live choice into a trailing one whose weight had underflowed to 0. A row on which that did not happen keeps
+// its index: every step up to a live choice has that choice's weight beyond it. Compares only, no branch and
+// no data-dependent address.
+template <int NH>
+__device__ __forceinline__ int categorical_index(const float (&ex)[NH], float sum, float u, int n_choices)
+{
+    bool more[NH - 1];  // more[q]: some ex beyond q is positive
+    bool m = false;
+#pragma unroll
+    for (int q = NH - 2; q >= 0; --q) {
+        m = m | (ex[q + 1] > 0.0f);
+        more[q] = m;
+    }
+    int index = 0;
+    float cdf = 0.0f;
+#pragma unroll
+    for (int q = 0; q < NH - 1; ++q) {
+        cdf += ex[q] / sum;
+        index += ((q < n_choices - 1) & (cdf <= u) & more[q]) ? 1 : 0;
+    }
+    return index;
+}
+
 struct ResetStream {
     uint32_t x, y, z, w;
     // next uniform in [0, 1) with 24 random bits

@@ -135,14 +135,9 @@
         }
         const float lse = logf(sum);
         const float u = (float)(mix32(key) >> 8) * 0x1p-24f;  // one uniform per env, [0, 1)
-        // index = the number of q in 0 .. K - 2 whose running sum p_0 + .. + p_q is <= u
-        int index = 0;
-        float cdf = 0.0f;
-#pragma unroll
-        for (int q = 0; q < NH - 1; ++q) {
-            cdf += ex[q] / sum;
-            index += (q < n_choices - 1 && cdf <= u) ? 1 : 0;
-        }
+        // index = the number of q in 0 .. K - 2 whose running sum p_0 + .. + p_q is <= u and which have a
+        // positive weight beyond them: a choice whose weight underflowed to 0 is never drawn
+        const int index = categorical_index(ex, sum, u, n_choices);
         // the chosen logit and the table row by compares: no data-dependent address
         float za = mean[0], a_env[NA] = {tab.v[0][0], tab.v[0][1]};
 #pragma unroll

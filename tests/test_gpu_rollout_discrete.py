@@ -129,7 +129,11 @@ def test_heads_past_k_stay_out(k):
 
 def test_underflowing_probability():
     """K = 4 with the last bias at -120: exp(z_3 - max) underflows to 0 in fp32 (e^-103 is the smallest
-    subnormal); every stored log-prob is finite and the paths agree on them."""
+    subnormal); every stored log-prob is finite and the paths agree on them. A choice whose fp32 weight is 0 is
+    never drawn, at any u: the sampler counts a step past choice q only while some weight beyond q is positive
+    (categorical_index, rocket_device.h). These 2 x 2 400 random draws would not see a sampler without that
+    rule, which drew such a choice only at u >= 1 - 3 x 2^-24; tests/test_gpu_discrete_sampler.py runs those
+    draws on every entry point."""
     import torch
     from discrete_ref import cat_policy
 
